@@ -8,10 +8,20 @@ device-resident entry points, x and y resident in HBM.  Metric: GFLOP/s =
 roofline object (algorithmic bytes per launch / average launch duration).
 
 Protocol (reference harness, src/bench/Bench.cpp:29-30 and
-src/bench/SparsexModule.cpp:65-79): after the warm-up, 5 batches of --steps
-SpMVs each; every batch is bracketed by a barrier + device synchronisation on
-both sides and timed on the host and with HIP events on the launch stream; the
-time of a batch is the maximum over the ranks; the MEDIAN batch is reported.
+src/bench/SparsexModule.cpp:65-79): after the warm-up, the --steps timed SpMVs
+in 5 batches (fewer when there are fewer steps); every batch is bracketed by a
+barrier + device synchronisation on both sides and timed on the host and with
+HIP events on the launch stream; the time of a batch is the maximum over the
+ranks; the MEDIAN batch's time per step is reported (ms_per_step).  Of the
+equivalent ways to launch the steps (hipGraph replay or stream launches; on
+several ranks the halo exchange in rounds or after the product) one short
+batch each, before the timed steps, picks the one that is timed.
+
+A plain run does only that: set-up, warm-up, the timed steps, (--dump-outputs
+DIR) what the last step computed as DIR/*.npy, and the JSON line.  --full adds
+everything else: the parity gates against the CSR product, the other launch
+forms, the beta call, the measured roofs, the host-vector entry points, the
+CPU baseline and the other configurations.
 
 Workload: ONE fixed global matrix -- `syn-nlpkkt`, the stand-in for SuiteSparse
 nlpkkt240 (BASELINE.json configs[4]) at a grid edge that fits one GPU and lies
@@ -22,9 +32,10 @@ it owns (spx.rt.row_offset / spx.rt.global_rows), holds the full x and completes
 its own rows of y: the general path needs nothing from the other ranks, the
 symmetric path (--symmetric) hands the sums it formed for rows in front of its
 own -- the reference's conflict map -- to their owners through RCCL
-point-to-point inside the library (spx_hip_matvec_dist).  At N = 1 the line also
-carries a "configs" object with the other BASELINE configurations (cant, nd24k on
-the symmetric path, webbase-1M; synthetic stand-ins) measured the same way.
+point-to-point inside the library (spx_hip_matvec_dist).  With --full at N = 1
+the line also carries a "configs" object with the other BASELINE configurations
+(cant, nd24k on the symmetric path, webbase-1M; synthetic stand-ins) measured
+the same way.
 """
 import argparse
 import json
@@ -42,6 +53,10 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (guides/MI355X_MICROARCH.md)
 MALL_BYTES = 256 << 20  # Infinity Cache
 ALPHA = 0.5
 BATCHES = 5             # OUTER_LOOPS of the reference harness
+TRIAL_STEPS = 32        # steps of the short batch that picks the launch form before the timed steps
+DUMP_SAMPLE = 1 << 21   # --dump-outputs: rows of y written when the whole of y is larger than DUMP_WHOLE_MAX
+DUMP_WHOLE_MAX = 1 << 22
+DUMP_SEED = 0x5EED
 REF_BASELINE_THREADS = [8, 16, 32, 64, 128]   # the counts cpu_baseline() may try (the largest three the host has cores for)
 DEFAULT_EDGE = 240      # syn-nlpkkt grid edge = nlpkkt240's: 27 993 600 rows, 769 M nonzeros (nlpkkt240: 760.6 M), 6.2 GB of values
 SAMPLE_EDGE = 150       # its CPU-baseline sample: the same generator at 1/4 of the nonzeros (187 M, 1.5 GB of values:
@@ -809,40 +824,73 @@ def parity_gate(torch, y, a_local, xh, lo, hi, ablation):
             "criterion": "rel <= 1e-6 (reference Vector.cpp:51-57) and |err| <= 64*2^-53*sum|a||x|"}
 
 
-def time_batches(torch, step, steps, barrier, reduce_max, use_graph):
-    """BATCHES batches of `steps` steps -> (median wall seconds per batch over the
-    ranks' maxima, median HIP-event seconds per batch, graph used, all wall times)."""
-    graph = None
-    if use_graph:
-        # the library only enqueues kernels on the stream it is handed, so a
-        # whole solver loop can be captured; here: the K SpMVs of a batch
-        try:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+def split_steps(steps):
+    """The batch sizes of `steps` timed steps: BATCHES batches (fewer when there are fewer steps)
+    whose sizes differ by one at most, so that the batches hold exactly `steps` steps."""
+    nb = max(1, min(BATCHES, steps))
+    return [steps // nb + (1 if i < steps % nb else 0) for i in range(nb)]
+
+
+def capture_graphs(torch, step, sizes):
+    """{batch size: hipGraph of that many captured steps} for the sizes given, or None where this
+    stack cannot capture.  The library only enqueues kernels on the stream it is handed, so a whole
+    solver loop can be captured; here: the steps of a batch."""
+    graphs = {}
+    try:
+        for k in sorted(set(sizes)):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
                 cap = torch.cuda.current_stream().cuda_stream
-                for _ in range(steps):
+                for _ in range(k):
                     step(cap)
-            graph.replay()                  # instantiate + upload outside the timed region
-        except Exception as e:              # no capture on this stack: plain launches
-            print("hipGraph capture failed (%s); timing stream launches" % e, file=sys.stderr)
-            graph = None
+            g.replay()                      # instantiate + upload outside the timed region
+            graphs[k] = g
+    except Exception as e:                  # no capture on this stack: plain launches
+        print("hipGraph capture failed (%s); timing stream launches" % e, file=sys.stderr)
+        return None
+    return graphs
+
+
+def time_batches(torch, step, sizes, barrier, reduce_max, graphs=None):
+    """One batch per entry of `sizes` (that many steps each; replays of `graphs[size]` where given,
+    else stream launches) -> (median wall seconds per step over the batches, each batch the maximum
+    over the ranks; median HIP-event seconds per step; the wall seconds of every batch)."""
     stream = torch.cuda.current_stream().cuda_stream
-    walls, devs = [], []
-    for _ in range(BATCHES):
+    walls, per_step, devs = [], [], []
+    for k in sizes:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         barrier()
         t0 = time.perf_counter()
         ev0.record()
-        if graph is not None:
-            graph.replay()
+        if graphs is not None:
+            graphs[k].replay()
         else:
-            for _ in range(steps):
+            for _ in range(k):
                 step(stream)
         ev1.record()
         barrier()
-        walls.append(reduce_max(time.perf_counter() - t0))
-        devs.append(1e-3 * ev0.elapsed_time(ev1))       # HIP events on the launch stream
-    return float(np.median(walls)), float(np.median(devs)), graph is not None, walls
+        w = reduce_max(time.perf_counter() - t0)
+        walls.append(w)
+        per_step.append(w / k)
+        devs.append(1e-3 * ev0.elapsed_time(ev1) / k)       # HIP events on the launch stream
+    return float(np.median(per_step)), float(np.median(devs)), walls
+
+
+def pick_launch_form(torch, forms, trial, barrier, reduce_max):
+    """Of several equivalent ways to run the steps (hipGraph replay or stream launches; on several
+    ranks the halo exchange in rounds or after the product), the one a caller would take: each is
+    timed over one batch of `trial` steps and the fastest is returned, as (name, step, graphs, the
+    trial's ms per step of every form).  The ranks agree, as every batch time is their maximum."""
+    if len(forms) == 1:
+        return forms[0] + ({},)
+    trials = {}
+    best = None
+    for name, step, graphs in forms:
+        sec, _, _ = time_batches(torch, step, [trial], barrier, reduce_max, graphs)
+        trials[name] = round(1e3 * sec, 6)
+        if best is None or sec < best[0]:
+            best = (sec, name, step, graphs)
+    return best[1], best[2], best[3], trials
 
 
 def algorithmic_bytes(symmetric, nnz_local_full, rows_local, n, lower_local=None):
@@ -851,6 +899,31 @@ def algorithmic_bytes(symmetric, nnz_local_full, rows_local, n, lower_local=None
     if symmetric:
         return 8.0 * (lower_local + rows_local) + 8.0 * n + 8.0 * rows_local
     return 8.0 * nnz_local_full + 8.0 * n + 8.0 * rows_local
+
+
+def dump_outputs(dump_dir, torch, dist, y, wl, world, rank):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step -- y, the rows
+    the ranks own -- as DIR/y.npy (float64).  Where y holds more than DUMP_WHOLE_MAX rows, a fixed sample
+    of DUMP_SAMPLE of them (seeded, the same for every run of the same matrix size) is written instead,
+    with their row numbers in DIR/y_rows.npy (float64, exact).  Several ranks: rank 0 writes the rows
+    of all of them."""
+    n, lo, hi = wl.n, wl.lo, wl.hi
+    rows = None
+    if n > DUMP_WHOLE_MAX:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        mine = rows[(rows >= lo) & (rows < hi)]
+        vals = y[torch.from_numpy(mine).to(y.device)].cpu().numpy()
+    else:
+        vals = y[lo:hi].cpu().numpy()
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, vals)
+        vals = np.concatenate(parts)            # (the ranks own consecutive rows, in rank order)
+    if rank == 0:
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "y.npy"), np.ascontiguousarray(vals, dtype=np.float64))
+        if rows is not None:
+            np.save(os.path.join(dump_dir, "y_rows.npy"), rows.astype(np.float64))
 
 
 def run_config(torch, sx, name, symmetric, steps, warmup, cpu_budget, T, csr=None, traffic_key=None,
@@ -882,11 +955,15 @@ def run_config(torch, sx, name, symmetric, steps, warmup, cpu_budget, T, csr=Non
     parity = parity_gate(torch, y, a, xh, 0, n, os.environ.get("SPX_BENCH_ABLATION") == "1")
     for _ in range(warmup):
         step(torch.cuda.current_stream().cuda_stream)
-    wall, devs, graphed, _ = time_batches(torch, step, steps, torch.cuda.synchronize, lambda v: v, True)
+    sizes = [steps] * BATCHES
+    graphs = capture_graphs(torch, step, sizes)
+    sec, launch_s, _ = time_batches(torch, step, sizes, torch.cuda.synchronize, lambda v: v, graphs)
+    graphed = graphs is not None
     if graphed:
-        wall2, devs2, _, _ = time_batches(torch, step, steps, torch.cuda.synchronize, lambda v: v, False)
-        if wall2 < wall:                     # (the faster of graph replay and stream launches, as in the main line)
-            wall, devs, graphed = wall2, devs2, False
+        sec2, launch2, _ = time_batches(torch, step, sizes, torch.cuda.synchronize, lambda v: v)
+        if sec2 < sec:                       # (the faster of graph replay and stream launches)
+            sec, launch_s, graphed = sec2, launch2, False
+    del graphs
     lower = None
     if symmetric:
         # strictly lower nonzeros, row by row in chunks (no nnz-long temporaries)
@@ -896,8 +973,7 @@ def run_config(torch, sx, name, symmetric, steps, warmup, cpu_budget, T, csr=Non
             rows = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(rp[r0:r1 + 1]))
             lower += int((ci[rp[r0]:rp[r1]] < rows).sum())
     b_alg = algorithmic_bytes(symmetric, nnz, n, n, lower)
-    launch_s = devs / steps
-    out = {"gflops": round(2.0 * nnz * steps / wall / 1e9, 2), "us_per_spmv": round(1e6 * wall / steps, 3),
+    out = {"gflops": round(2.0 * nnz / sec / 1e9, 2), "us_per_spmv": round(1e6 * sec, 3),
            "nnz": nnz, "nrows": n, "symmetric_path": symmetric,
            "launch": "hipGraph replay" if graphed else "stream launches",
            "data": "file: " + os.path.basename(mtx) if mtx else "synthetic",
@@ -990,10 +1066,12 @@ def make_transport(ctx):
             "STAND-BY: torch.distributed all_to_all_single (RCCL) staged through device buffers")
 
 
-def run_path(ctx, args, symmetric):
-    """Generates this rank's rows, tunes them, (several ranks) attaches the exchange plan, gates
-    the product against CSR and times it.  Returns the facts of the path; rank 0's carry the line."""
+def run_path(ctx, args, symmetric, dump_dir=None):
+    """Generates this rank's rows, tunes them, (several ranks) attaches the exchange plan, (--full) gates
+    the product against CSR, times it and (`dump_dir`) writes what the last timed step computed.  Returns
+    the facts of the path; rank 0's carry the line."""
     torch, dist, sx = ctx["torch"], ctx["dist"], ctx["sx"]
+    full = args.full
     rank, world, dev = ctx["rank"], ctx["world"], ctx["dev"]
     barrier, reduce_max = ctx["barrier"], ctx["reduce_max"]
     from sparsex_amd import synth
@@ -1064,75 +1142,97 @@ def run_path(ctx, args, symmetric):
     def step_local(stream):                  # the kernels alone, no exchange at all
         A.hip_matvec_mult(ALPHA, x.data_ptr(), y.data_ptr(), stream)
 
-    # correctness gate before timing: this rank's rows against the CSR product
-    # (kernel ablations built by tools/build_variant.sh compute wrong results on
-    # purpose; their lines are marked and never a bench result)
+    # the first product on its own (on several ranks: the first exchange, bounded by the watchdog)
+    # (kernel ablations built by tools/build_variant.sh compute wrong results on purpose; their
+    # lines are marked and never a bench result)
     ablation = os.environ.get("SPX_BENCH_ABLATION") == "1"
     cur = torch.cuda.current_stream().cuda_stream
     with Watchdog(SETUP_TIMEOUT_S, "the first product (first exchange)"):
         step_owned(cur) if world > 1 else step(cur)
         torch.cuda.synchronize()
-    a_local = wl.local_csr()
-    parity = parity_gate(torch, y, a_local, xh, lo, hi, ablation)
-    halo = None
-    if world > 1:
-        # ... and, with the slices handed round, all of y on every rank
-        step_gather(cur)
-        torch.cuda.synchronize()
-        chk = torch.tensor([float(torch.nan_to_num(y, nan=1e300).abs().sum())], dtype=torch.float64,
-                           device=dev if ctx["backend"] == "nccl" else "cpu")
-        sums = [torch.zeros_like(chk) for _ in range(world)]
-        dist.all_gather(sums, chk)
-        assert all(abs(float(s) - float(sums[0])) <= 1e-9 * abs(float(sums[0])) for s in sums), \
-            "gathered y differs between the ranks"
-        parity_gate(torch, y, a_local, xh, lo, hi, ablation)
-        # ... and the halo exchange: into a vector of NaNs; the own rows pass the gate again, and
-        # every entry this rank's rows read as x equals what the hand-round of whole slices brought
-        halo = A.dist_halo()
-        y_full = y.clone()
-        y.fill_(float("nan"))
-        step(cur)
-        torch.cuda.synchronize()
-        parity_gate(torch, y, a_local, xh, lo, hi, ablation)
-        hc = torch.from_numpy(halo["recv_cols"]).to(dev)
-        scale = float(torch.nan_to_num(y_full).abs().max())
-        herr = float((y[hc] - y_full[hc]).abs().max()) if hc.numel() else 0.0
-        assert ablation or (herr == herr and herr <= 1e-12 * scale), "halo entries differ from the gathered y: %g" % herr
-        need = np.unique(a_local.indices)
-        need = need[(need < lo) | (need >= hi)]
-        if symmetric:
-            need = need[need < lo]              # (the stored triangle's columns)
-        assert np.array_equal(need, halo["recv_cols"]), "halo list != columns the rank's rows read"
-        if FULL != sx.SPX_DIST_HALO_X:
-            # ... and the plain order (whole product, then the exchange) once more, the same way
+    parity = None
+    halo = A.dist_halo() if world > 1 else None
+    if full:
+        # --full: correctness gate before timing, this rank's rows against the CSR product
+        a_local = wl.local_csr()
+        parity = parity_gate(torch, y, a_local, xh, lo, hi, ablation)
+        if world > 1:
+            # ... and, with the slices handed round, all of y on every rank
+            step_gather(cur)
+            torch.cuda.synchronize()
+            chk = torch.tensor([float(torch.nan_to_num(y, nan=1e300).abs().sum())], dtype=torch.float64,
+                               device=dev if ctx["backend"] == "nccl" else "cpu")
+            sums = [torch.zeros_like(chk) for _ in range(world)]
+            dist.all_gather(sums, chk)
+            assert all(abs(float(s) - float(sums[0])) <= 1e-9 * abs(float(sums[0])) for s in sums), \
+                "gathered y differs between the ranks"
+            parity_gate(torch, y, a_local, xh, lo, hi, ablation)
+            # ... and the halo exchange: into a vector of NaNs; the own rows pass the gate again, and
+            # every entry this rank's rows read as x equals what the hand-round of whole slices brought
+            y_full = y.clone()
             y.fill_(float("nan"))
-            step_halo_plain(cur)
+            step(cur)
             torch.cuda.synchronize()
             parity_gate(torch, y, a_local, xh, lo, hi, ablation)
+            hc = torch.from_numpy(halo["recv_cols"]).to(dev)
+            scale = float(torch.nan_to_num(y_full).abs().max())
             herr = float((y[hc] - y_full[hc]).abs().max()) if hc.numel() else 0.0
-            assert ablation or (herr == herr and herr <= 1e-12 * scale), "halo entries (plain order) differ: %g" % herr
-        del y_full, hc
-    del a_local
+            assert ablation or (herr == herr and herr <= 1e-12 * scale), "halo entries differ from the gathered y: %g" % herr
+            need = np.unique(a_local.indices)
+            need = need[(need < lo) | (need >= hi)]
+            if symmetric:
+                need = need[need < lo]              # (the stored triangle's columns)
+            assert np.array_equal(need, halo["recv_cols"]), "halo list != columns the rank's rows read"
+            if FULL != sx.SPX_DIST_HALO_X:
+                # ... and the plain order (whole product, then the exchange) once more, the same way
+                y.fill_(float("nan"))
+                step_halo_plain(cur)
+                torch.cuda.synchronize()
+                parity_gate(torch, y, a_local, xh, lo, hi, ablation)
+                herr = float((y[hc] - y_full[hc]).abs().max()) if hc.numel() else 0.0
+                assert ablation or (herr == herr and herr <= 1e-12 * scale), "halo entries (plain order) differ: %g" % herr
+            del y_full, hc
+        del a_local
 
     for _ in range(args.warmup):
         step(cur)
     barrier()
-    use_graph = args.graph and world == 1
-    wall, devs, graphed, walls = time_batches(torch, step, args.steps, barrier, reduce_max, use_graph)
-    launch_modes = None
-    if graphed:
-        # the same K steps as plain stream launches: a caller can do either, the line reports the
-        # faster of the two protocols and shows both (on a 1.2 ms kernel the replay of a captured
-        # graph has been seen 10 % slower AND 3 % faster than stream launches on the same box)
-        wall2, devs2, _, walls2 = time_batches(torch, step, args.steps, barrier, reduce_max, False)
-        launch_modes = {"hipGraph_ms_per_step": round(1e3 * wall / args.steps, 6),
-                        "stream_launches_ms_per_step": round(1e3 * wall2 / args.steps, 6)}
-        if wall2 < wall:
-            wall, devs, graphed, walls = wall2, devs2, False, walls2
-    # the reference bench's own call (src/bench/SparsexModule.cpp:54-71): y <- ALPHA*A*x + BETA*y on tuned
-    # vectors, timed the same way (one more read of y per product)
-    kernel_call = None
-    if world == 1:
+    # the timed steps: exactly --steps of them, in up to BATCHES batches.  Equivalent ways to run
+    # them -- one GPU: the replay of a captured hipGraph or stream launches (on a 1.2 ms kernel the
+    # replay has been seen 10 % slower AND 3 % faster than stream launches on the same box); several
+    # ranks: the halo exchange in rounds behind the parts of the product or after the whole product --
+    # leave the same y, so a caller takes the faster: each is tried over one short batch first
+    sizes = split_steps(args.steps)
+    trial = min(sizes[0], TRIAL_STEPS)
+    graphs = capture_graphs(torch, step, sizes + [trial]) if args.graph and world == 1 else None
+    forms = []
+    if graphs is not None:
+        forms.append(("hipGraph", step, graphs))
+    rounds = world > 1 and FULL != sx.SPX_DIST_HALO_X
+    forms.append(("stream_launches" if world == 1 else "halo_in_rounds" if rounds else "halo_after_product", step, None))
+    if rounds:
+        forms.append(("halo_after_product", step_halo_plain, None))
+    form, step_t, graphs_t, trials = pick_launch_form(torch, forms, trial, barrier, reduce_max)
+    sec, dev_s, walls = time_batches(torch, step_t, sizes, barrier, reduce_max, graphs_t)
+    graphed = graphs_t is not None
+    if dump_dir:
+        dump_outputs(dump_dir, torch, dist, y, wl, world, rank)
+
+    launch_s = dev_s if world == 1 else None
+    launch_modes = kernel_call = collective = None
+    if full and graphed:
+        # --full: the same steps as plain stream launches as well (a caller can do either)
+        sec2, _, _ = time_batches(torch, step, sizes, barrier, reduce_max)
+        launch_modes = {"hipGraph_ms_per_step": round(1e3 * sec, 6),
+                        "stream_launches_ms_per_step": round(1e3 * sec2, 6)}
+    elif full and world == 1 and graphs is not None:
+        sec2, _, _ = time_batches(torch, step, sizes, barrier, reduce_max, graphs)
+        launch_modes = {"hipGraph_ms_per_step": round(1e3 * sec2, 6),
+                        "stream_launches_ms_per_step": round(1e3 * sec, 6)}
+    del graphs, graphs_t
+    # --full: the reference bench's own call (src/bench/SparsexModule.cpp:54-71): y <- ALPHA*A*x + BETA*y on
+    # tuned vectors, timed the same way (one more read of y per product)
+    if full and world == 1:
         BETA = 0.5
         ref = None
         if not ablation:
@@ -1149,40 +1249,38 @@ def run_path(ctx, args, symmetric):
 
         def step_kernel(stream):
             A.hip_matvec_kernel(ALPHA, x.data_ptr(), BETA, y.data_ptr(), stream)
-        wk, dk, _, _ = time_batches(torch, step_kernel, args.steps, barrier, reduce_max, False)
+        sk, dk, _ = time_batches(torch, step_kernel, sizes, barrier, reduce_max)
         kernel_call = {"call": "spx_hip_matvec_kernel(alpha=%.1f, A, x, beta=%.1f, y)" % (ALPHA, BETA),
-                       "ms_per_step": round(1e3 * wk / args.steps, 6), "gflops": round(2.0 * wl.nnz * args.steps / wk / 1e9, 2),
-                       "avg_launch_us": round(1e6 * dk / args.steps, 3),
+                       "ms_per_step": round(1e3 * sk, 6), "gflops": round(2.0 * wl.nnz / sk / 1e9, 2),
+                       "avg_launch_us": round(1e6 * dk, 3),
                        "reference": "src/bench/SparsexModule.cpp:54-71"}
         del ref
-    collective = None
-    launch_s = devs / args.steps
-    if world > 1:
-        w_owned, _, _, _ = time_batches(torch, step_owned, args.steps, barrier, reduce_max, False)
-        w_gather, _, _, _ = time_batches(torch, step_gather, args.steps, barrier, reduce_max, False)
-        w_plain, walls_plain = wall, walls
-        if FULL != sx.SPX_DIST_HALO_X:
-            w_plain, _, _, walls_plain = time_batches(torch, step_halo_plain, args.steps, barrier, reduce_max, False)
-        w_local, d_local, _, _ = time_batches(torch, step_local, args.steps, barrier, reduce_max, False)
-        launch_s = d_local / args.steps       # the roofline is the kernels' (HIP events, this rank)
-        gf = lambda w: round(2.0 * wl.nnz * args.steps / w / 1e9, 2)
+    if full and world > 1:
+        s_owned, _, _ = time_batches(torch, step_owned, sizes, barrier, reduce_max)
+        s_gather, _, _ = time_batches(torch, step_gather, sizes, barrier, reduce_max)
         # the halo step in rounds behind the parts of the product and the same exchange after the whole
-        # product leave the ranks in the same state: a caller picks the faster, so does `value`
-        w_rounds = wall
+        # product leave the ranks in the same state: `value` is the faster (above); here both
+        s_rounds = s_plain = sec
+        if rounds and form == "halo_in_rounds":
+            s_plain, _, _ = time_batches(torch, step_halo_plain, sizes, barrier, reduce_max)
+        elif rounds:
+            s_rounds, _, _ = time_batches(torch, step, sizes, barrier, reduce_max)
+        s_local, d_local, _, = time_batches(torch, step_local, sizes, barrier, reduce_max)
+        launch_s = d_local                     # the roofline is the kernels' (HIP events, this rank)
+        gf = lambda s: round(2.0 * wl.nnz / s / 1e9, 2)
         step_form = "halo exchange in rounds behind the parts of the product (SPX_DIST_HALO_X | SPX_DIST_OVERLAP)" \
-            if FULL != sx.SPX_DIST_HALO_X else "halo exchange after the product (SPX_DIST_HALO_X)"
-        if w_plain < wall:
-            wall, walls = w_plain, walls_plain
+            if rounds else "halo exchange after the product (SPX_DIST_HALO_X)"
+        if rounds and form == "halo_after_product":
             step_form = "halo exchange after the whole product (SPX_DIST_HALO_X; measured faster than in rounds)"
-        collective = {"full_step_gflops": gf(wall), "owned_rows_only_gflops": gf(w_owned), "full_step_form": step_form,
-                      "halo_step_in_rounds_ms": round(1e3 * w_rounds / args.steps, 5),
-                      "gather_y_step_gflops": gf(w_gather), "kernels_only_gflops": gf(w_local),
-                      "full_step_ms": round(1e3 * wall / args.steps, 5),
-                      "owned_rows_only_ms": round(1e3 * w_owned / args.steps, 5),
-                      "gather_y_step_ms": round(1e3 * w_gather / args.steps, 5),
-                      "halo_step_not_overlapped_ms": round(1e3 * w_plain / args.steps, 5),
+        collective = {"full_step_gflops": gf(sec), "owned_rows_only_gflops": gf(s_owned), "full_step_form": step_form,
+                      "halo_step_in_rounds_ms": round(1e3 * s_rounds, 5),
+                      "gather_y_step_gflops": gf(s_gather), "kernels_only_gflops": gf(s_local),
+                      "full_step_ms": round(1e3 * sec, 5),
+                      "owned_rows_only_ms": round(1e3 * s_owned, 5),
+                      "gather_y_step_ms": round(1e3 * s_gather, 5),
+                      "halo_step_not_overlapped_ms": round(1e3 * s_plain, 5),
                       "overlap_rounds": len(A.dist_rounds()) if FULL != sx.SPX_DIST_HALO_X else 0,
-                      "kernels_only_ms": round(1e3 * w_local / args.steps, 5),
+                      "kernels_only_ms": round(1e3 * s_local, 5),
                       "halo_bytes_received_per_rank": 8 * int(halo["recv_cols"].size),
                       "halo_bytes_sent_per_rank": 8 * int(halo["send_rows"].size),
                       "y_handround_bytes_received_per_rank": 8 * (n - (hi - lo)),
@@ -1198,7 +1296,7 @@ def run_path(ctx, args, symmetric):
             "balance_nnz": wl.lower_local + (hi - lo) if symmetric else wl.nnz_local,   # what the rows were dealt by
             "nnz_stored": int(info.nnz_stored), "rowblocks": int(info.n_rowblocks),
             "tune_seconds": round(info.tune_seconds, 2), "emit_upload_seconds": round(info.emit_seconds, 2),
-            "kernels_us": round(1e6 * launch_s, 2),
+            "kernels_us": round(1e6 * launch_s, 2) if launch_s is not None else None,
             "conflict_rows_sent": int(plan["send_rows"].size) if world > 1 else 0,
             "conflict_entries_received": int(plan["n_recv"]) if world > 1 else 0,
             "halo_entries_received": int(halo["recv_cols"].size) if world > 1 else 0,
@@ -1211,7 +1309,6 @@ def run_path(ctx, args, symmetric):
 
     rows_local = hi - lo
     b_alg = algorithmic_bytes(symmetric, wl.nnz_local, rows_local, n, wl.lower_local)
-    achieved = b_alg / launch_s / 1e9
     tkey = "%s%s%s" % (args.workload, "-e%d" % args.edge if args.workload in SLICED else "",
                        "-sym" if symmetric else "")
     std = world == 1 and args.scale == 1.0 and not args.opt and not wl.mtx
@@ -1226,17 +1323,43 @@ def run_path(ctx, args, symmetric):
               "rank sends the sums for its conflict rows (rows in front of its own that its lower triangle " \
               "touches) to their owners, packed, pairwise (no n-long all-reduce)%s" % (
                   world, "s" if world > 1 else "", "; then the halo exchange of y" if world > 1 else "")
+    roofline = {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "kernel": kernel_name(info, symmetric, world),
+                "algorithmic_bytes_per_launch": int(b_alg),
+                "cache_resident": bool(info.value_bytes + info.index_bytes < MALL_BYTES),
+                "scope": "rank 0's GPU: its stored values, x and its rows of y once per launch"
+                         + (" (kernels only: timed without the exchange)" if world > 1 else "")}
+    if launch_s is not None:
+        achieved = b_alg / launch_s / 1e9
+        roofline.update({
+            "achieved": round(achieved, 2), "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": measured_traffic(tkey, kernel_name(info, symmetric, world)) if std else None,
+            "traffic_range": traffic_range(tkey, kernel_name(info, symmetric, world), info) if std else None,
+            "traffic_source": traffic_note(tkey, kernel_name(info, symmetric, world)) if std else None,
+            "avg_launch_us": round(1e6 * launch_s, 3),
+            # (the same stream runs at different speeds on different nodes and at different times, at
+            # identical reported clocks: profiles/r04/spread.md; the line says where this run lies)
+            "spread_group": (("%.2f ms here; the boxes of round 4 ran this very stream in 1.19-1.40 ms (%s third of that "
+                              "range; profiles/r04/spread.md)" % (1e3 * launch_s, "fastest" if launch_s < 1.26e-3 else (
+                                  "middle" if launch_s < 1.33e-3 else "slowest")))
+                             if world == 1 and not symmetric and args.workload == "syn-nlpkkt" and args.edge == DEFAULT_EDGE
+                             and not wl.mtx else None)})
+    else:
+        roofline["note"] = "several ranks: the kernels-only timing the roofline needs is a run of its own (--full)"
     out = {
-        "value": round(2.0 * wl.nnz * args.steps / wall / 1e9, 3),
-        "ms_per_step": round(1e3 * wall / args.steps, 6),
+        "value": round(2.0 * wl.nnz / sec / 1e9, 3),
+        "ms_per_step": round(1e3 * sec, 6),
         "data": "file" if wl.mtx else "synthetic",
-        "protocol": {"batches": BATCHES, "steps_per_batch": args.steps, "reported": "median batch "
-                     "(max over ranks per batch)", "batch_ms": [round(1e3 * w, 4) for w in walls],
+        "protocol": {"timed_steps": args.steps, "batches": len(sizes), "steps_per_batch": sizes,
+                     "reported": "median over the batches of the time per step (max over ranks per batch)",
+                     "batch_ms": [round(1e3 * w, 4) for w in walls],
+                     "launch_form": form, "launch_form_trial_ms_per_step": trials or None,
+                     "launch_form_trial_steps": trial if trials else 0,
                      "launch_modes": launch_modes,
                      "reference": "src/bench/Bench.cpp:29-30, SparsexModule.cpp:65-79"},
         "config": {"workload": wl.label, "nrows": n, "nnz": wl.nnz,
                    "symmetric_path": bool(symmetric), "partitions_per_gpu": T,
-                   "launch": "one hipGraph of %d captured launches per batch" % args.steps if graphed
+                   "launch": "hipGraph replays of the captured steps of a batch" if graphed
                              else "stream launches",
                    "parallelism": par, "transport": ctx["transport_name"],
                    "collective_in_value": ("included: every step ends with each rank holding its rows of y and the "
@@ -1247,24 +1370,7 @@ def run_path(ctx, args, symmetric):
                    "input": ("spx_input_load_mmf(%s)" % os.path.basename(wl.mtx)) if load_s is not None else "spx_input_load_csr",
                    "dist_reorder": wl.reorder,
                    "dist_reorder_seconds": round(wl.reorder_seconds, 2)},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": measured_traffic(tkey, kernel_name(info, symmetric, world)) if std else None,
-                     "traffic_range": traffic_range(tkey, kernel_name(info, symmetric, world), info) if std else None,
-                     "traffic_source": traffic_note(tkey, kernel_name(info, symmetric, world)) if std else None,
-                     "kernel": kernel_name(info, symmetric, world),
-                     "algorithmic_bytes_per_launch": int(b_alg),
-                     "avg_launch_us": round(1e6 * launch_s, 3),
-                     # (the same stream runs at different speeds on different nodes and at different times, at
-                     # identical reported clocks: profiles/r04/spread.md; the line says where this run lies)
-                     "spread_group": (("%.2f ms here; the boxes of round 4 ran this very stream in 1.19-1.40 ms (%s third of that "
-                                       "range; profiles/r04/spread.md)" % (1e3 * launch_s, "fastest" if launch_s < 1.26e-3 else (
-                                           "middle" if launch_s < 1.33e-3 else "slowest")))
-                                      if world == 1 and not symmetric and args.workload == "syn-nlpkkt" and args.edge == DEFAULT_EDGE
-                                      and not wl.mtx else None),
-                     "cache_resident": bool(info.value_bytes + info.index_bytes < MALL_BYTES),
-                     "scope": "rank 0's GPU: its stored values, x and its rows of y once per launch"
-                              + (" (kernels only: timed without the exchange)" if world > 1 else "")},
+        "roofline": roofline,
         "format": {"nnz_stored": int(info.nnz_stored), "unit_elems": int(info.n_unit_elems),
                    "delta_elems": int(info.n_delta_elems), "units": int(info.n_units),
                    "rowblocks": int(info.n_rowblocks), "waves_per_workgroup": int(info.waves),
@@ -1274,13 +1380,14 @@ def run_path(ctx, args, symmetric):
                    "tune_seconds": round(info.tune_seconds, 3),
                    "emit_upload_seconds": round(info.emit_seconds, 3)},
         "ranks": per_rank,
-        "parity": parity,
     }
+    if parity is not None:
+        out["parity"] = parity
     if kernel_call:
         out["matvec_kernel"] = kernel_call
     if collective:
         out["collective"] = collective
-    if world == 1 and not symmetric:
+    if full and world == 1 and not symmetric:
         peak = measured_read_peak(sx, torch)
         out["roofline"]["measured_stream_read_peak"] = round(peak, 1)
         out["roofline"]["frac_of_measured_read_peak"] = round(achieved / peak, 4)
@@ -1290,7 +1397,7 @@ def run_path(ctx, args, symmetric):
         out["roofline"]["measured_mixed_peak"] = round(mixed, 1)
         out["roofline"]["mixed_peak_write_share"] = round(share, 4)
         out["roofline"]["frac_of_measured_mixed_peak"] = round(achieved / mixed, 4)
-    if world == 1 and rank == 0 and not args.no_host_api:
+    if full and world == 1 and rank == 0 and not args.no_host_api:
         out["host_api"] = host_api_rate(A, xh, n, wl.nnz)
     if ablation:
         out["INVALID_ablation_build"] = os.environ.get("SPX_LIB_PATH", "")
@@ -1340,7 +1447,9 @@ def self_launch(n, argv):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=128, help="SpMVs per batch (LOOPS); %d batches are timed" % BATCHES)
+    ap.add_argument("--steps", type=int, default=128,
+                    help="timed SpMVs, in %d batches (fewer when there are fewer steps); ms_per_step is the median "
+                         "batch's time per step" % BATCHES)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--workload", default="syn-nlpkkt", choices=["syn-cant", "syn-nd24k", "syn-webbase", "syn-nlpkkt", "syn-kkt2f", "syn-bandrandom"])
     ap.add_argument("--edge", type=int, default=DEFAULT_EDGE,
@@ -1353,15 +1462,22 @@ def main():
     ap.add_argument("--symmetric", action="store_true")
     ap.add_argument("--host-threads", type=int, default=0,
                     help="host preprocessing partitions per GPU (default: min(cores / ranks, 32))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the parity gates against the CSR product, "
+                         "the CPU baseline, the other configurations, both launch modes, the beta call, the "
+                         "measured roofs, the host-vector entry points and (several ranks) the other step forms")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (y, or a fixed sample of its "
+                         "rows where it is larger than %d rows) as DIR/<name>.npy" % DUMP_WHOLE_MAX)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="time the CPU baseline on the whole bench matrix instead of its edge-%d sample (a minute or two "
                          "more of host time and ~60 GB of host memory at edge 240)" % SAMPLE_EDGE)
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the host-vector entry points (host_api): under a profiler their part-by-part launches of the "
+                    help="--full: skip the host-vector entry points (host_api): under a profiler their part-by-part launches of the "
                          "same kernel would be averaged into the bench loop's")
     ap.add_argument("--no-configs", action="store_true",
-                    help="N = 1: skip the other BASELINE configurations (cant, nd24k symmetric, webbase); "
+                    help="--full, N = 1: skip the other BASELINE configurations (cant, nd24k symmetric, webbase); "
                          "N > 1: skip the second run on the symmetric path")
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="launch the steps of a batch one by one instead of replaying them as one hipGraph "
@@ -1373,6 +1489,8 @@ def main():
                          "several ranks -- P A P^T is the same operator, and a rank then reads a thin shell of its "
                          "neighbours' unknowns instead of a whole slice (profiles/r04/slices_one_gpu_proxy_e240_raw.md)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python3 bench.py --gpus N` (N > 1) started without a launcher: this process starts the N ranks itself,
     # before it has imported torch or touched a GPU, relays rank 0's line and leaves with the launcher's code
@@ -1440,7 +1558,7 @@ def main():
     if world > 1:
         ctx["transport"], ctx["transport_name"] = make_transport(ctx)
 
-    res, wl, T = run_path(ctx, args, args.symmetric)
+    res, wl, T = run_path(ctx, args, args.symmetric, args.dump_outputs)
     out = None
     if rank == 0:
         out = {"metric": "SpMV GFLOP/s (2*nnz/t, alpha=0.5, x/y resident in HBM)",
@@ -1454,7 +1572,8 @@ def main():
             # exchange went through another transport (gloo test path, the torch.distributed stand-by)
             tr = ctx["transport"]
             out["ranks_seen_by_rccl"] = tr.rccl_ranks() if hasattr(tr, "rccl_ranks") else None
-    if world > 1 and not args.symmetric and not args.no_configs and args.workload in SYMMETRIC_WORKLOADS and not args.mtx:
+    if world > 1 and args.full and not args.symmetric and not args.no_configs and args.workload in SYMMETRIC_WORKLOADS \
+            and not args.mtx:
         # the same matrix through the symmetric path in the same invocation: here the conflict rows
         # really travel (RCCL point-to-point) before the hand-round
         del wl
@@ -1465,7 +1584,7 @@ def main():
         ctx["transport"].destroy()
     n = wl.n
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # the whole bench matrix where the host allows it (T = all cores, the bench matrix):
             # 32 CPUs or more for this process and ~70 GB of free memory -- tuning the matrix a second time with one
             # partition per thread then takes about two minutes; else its edge-150 sample, labelled as such
@@ -1496,7 +1615,7 @@ def main():
                 SAMPLE_EDGE, int(csr_s[0][-1]), round(wl.nnz / max(int(csr_s[0][-1]), 1)))
                 if note.startswith("sample: syn-nlpkkt at grid edge") else "the whole bench matrix")
             del csr_s
-        if world == 1 and not args.no_configs and args.workload == "syn-nlpkkt" and not args.mtx:
+        if world == 1 and args.full and not args.no_configs and args.workload == "syn-nlpkkt" and not args.mtx:
             cfgs = {}
             if not args.symmetric and not args.opt:
                 # the bench matrix itself through the symmetric path (BASELINE config 4's path:

@@ -32,7 +32,7 @@ def run_bench(world, extra, port=None, timeout=900, host_threads=2):
     env.update({"SPX_BENCH_BACKEND": "gloo", "MASTER_ADDR": "127.0.0.1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--host-threads",
+           "--gpus", str(world), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--host-threads",
            str(host_threads)] + extra
     if world == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
@@ -220,7 +220,7 @@ def test_bench_starts_its_own_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--host-threads", "2", "--edge", "28"], env=env, cwd=ROOT,
+                        "--full", "--no-cpu-baseline", "--host-threads", "2", "--edge", "28"], env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + "\n" + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

@@ -6,7 +6,7 @@ fail=0
 run() {
   w=$1; shift
   port=$(python3 -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
-  out=$(timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $w --master-addr 127.0.0.1 --master-port $port bench.py --gpus $w --steps 3 --warmup 1 --no-cpu-baseline --host-threads 2 "$@" 2>&1 | grep -E '^\{"metric"|Error|error|assert' | head -3)
+  out=$(timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $w --master-addr 127.0.0.1 --master-port $port bench.py --gpus $w --steps 3 --warmup 1 --full --no-cpu-baseline --host-threads 2 "$@" 2>&1 | grep -E '^\{"metric"|Error|error|assert' | head -3)
   if echo "$out" | grep -q '^{"metric"'; then echo "ok   world $w $*  $(echo "$out" | python3 -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['parity']['max_err_over_fp64_bound'], d['roofline']['kernel'][:60])")"; else echo "FAIL world $w $*"; echo "$out" | cut -c1-300; fail=1; fi
 }
 for w in 2 3 4; do
