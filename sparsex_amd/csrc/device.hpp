@@ -1,5 +1,6 @@
 // device.hpp -- HBM-resident form of a tuned matrix and the launch entry
-// points of the HIP interpreter kernel (implemented in spmv_kernels.hip).
+// points of the HIP interpreter (implemented in device_runtime.cpp, which launches
+// the kernels of spmv_kernels.hip, spmv_xw_kernels.hip and spmv_sx_kernels.hip).
 //
 // Replaces the reference's JIT'd per-partition spmv_fn + thread-pool dispatch
 // (src/internals/CsxKernels.cpp:35-129, src/internals/CsxSpmv.cpp:28-86).

@@ -1,14 +1,14 @@
 // spmv_device.hpp -- device code shared by the kernels of the CSX interpreter (spmv_kernels.hip: the
 // general and the symmetric kernels; spmv_xw_kernels.hip: the general kernel with the unit windows of x
-// in LDS): kernel arguments, the XCD-aware row-block order, and the pass bodies -- one lane per row
-// segment, values interleaved, x gathered through L2 or read from the row-block's LDS window.
+// in LDS): the pass bodies -- one lane per row segment, values interleaved, x gathered through L2 or
+// read from the row-block's LDS window.  The kernel arguments and the launchers: spmv_launch.hpp.
 //
 // Semantics restated from the reference's SpMV templates (src/templates/csx_spmv_tmpl.c:66-101 and the
 // per-unit bodies delta/horiz/vert/diag/rdiag/block_row/block_col _tmpl.c).
 #pragma once
 
 #include "gpu_format.h"
-#include "xwindows.hpp"
+#include "spmv_launch.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -16,39 +16,6 @@
 #include <cstdint>
 
 namespace spx {
-
-struct KernelArgs {
-    const SpxRowBlock *rbs;
-    const SpxPass *passes;
-    const double *values;
-    const SpxUnitDesc *descs;
-    const uint8_t *cidx;
-    const uint16_t *segrows;
-    const double *x;
-    double *y;
-    double *carry;
-    const double *dvalues;   // symmetric, fused: diagonal added at the write-out (else null)
-    double *spill;           // symmetric tiles: transposed sums of columns owned by other row-blocks
-    const uint32_t *slot_col;  // ... or (atomic hand-over) the first column of every group of eight slots
-    double alpha, beta;
-    const double *dvalues_priv;   // atomic hand-over: diagonal for the row-blocks that store their rows
-    double beta_priv;             // ... and the caller's beta for them (beta above is 1 after the init pass)
-    uint32_t n_rb;
-    uint32_t pass_stride;    // pass headers of row-block i start at passes[i * pass_stride]
-    const XwEntry *xw_tab;   // unit windows of x (xwindows.hpp): XW_MAX entries per row-block, or null
-};
-
-// XCD-aware order of the row-blocks: workgroup b runs on XCD b % 8; XCD x walks the row-blocks
-// [first[x], first[x + 1]) in turn, a contiguous part of the matrix that holds an eighth of its
-// VALUES (not of its row-blocks: a symmetric KKT matrix keeps its stored triangle in the second
-// half of its rows, and an eighth of the row-blocks by count left five XCDs without work)
-struct XcdSplit {
-    uint32_t first[9];
-};
-
-// wavefronts per workgroup: the kernels exist for 2, 4 and 8 (spx.gpu.waves, or
-// measured at tune time: small matrices like 2, leftover-heavy ones 8)
-constexpr int MAX_WAVES_PER_BLOCK = 8;
 
 // Loads of the matrix stream (values, descriptors): plain loads.  (Marking them non-temporal, so that
 // they would not push x out of the L2, measured slower on every workload: profiles/r03/ablation.md

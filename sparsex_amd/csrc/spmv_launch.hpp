@@ -1,0 +1,84 @@
+// spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
+// XCD-aware row-block order, the kernel families and the launchers of the three interpreter translation
+// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip).  Plain C++: no HIP header, so that
+// the host runtime (device_runtime.cpp) is compiled by the host compiler.
+#pragma once
+
+#include "gpu_format.h"
+#include "xwindows.hpp"
+
+#include <cstddef>
+#include <cstdint>
+
+namespace spx {
+
+struct KernelArgs {
+    const SpxRowBlock *rbs;
+    const SpxPass *passes;
+    const double *values;
+    const SpxUnitDesc *descs;
+    const uint8_t *cidx;
+    const uint16_t *segrows;
+    const double *x;
+    double *y;
+    double *carry;
+    const double *dvalues;   // symmetric, fused: diagonal added at the write-out (else null)
+    double *spill;           // symmetric tiles: transposed sums of columns owned by other row-blocks
+    const uint32_t *slot_col;  // ... or (atomic hand-over) the first column of every group of eight slots
+    double alpha, beta;
+    const double *dvalues_priv;   // atomic hand-over: diagonal for the row-blocks that store their rows
+    double beta_priv;             // ... and the caller's beta for them (beta above is 1 after the init pass)
+    uint32_t n_rb;
+    uint32_t pass_stride;    // pass headers of row-block i start at passes[i * pass_stride]
+    const XwEntry *xw_tab;   // unit windows of x (xwindows.hpp): XW_MAX entries per row-block, or null
+};
+
+// XCD-aware order of the row-blocks: workgroup b runs on XCD b % 8; XCD x walks the row-blocks
+// [first[x], first[x + 1]) in turn, a contiguous part of the matrix that holds an eighth of its
+// VALUES (not of its row-blocks: a symmetric KKT matrix keeps its stored triangle in the second
+// half of its rows, and an eighth of the row-blocks by count left five XCDs without work)
+struct XcdSplit {
+    uint32_t first[9];
+};
+
+// wavefronts per workgroup: the kernels exist for 2, 4 and 8 (spx.gpu.waves, or
+// measured at tune time: small matrices like 2, leftover-heavy ones 8)
+constexpr int MAX_WAVES_PER_BLOCK = 8;
+
+// The kernels of spmv_kernels.hip that walk the row-blocks (one template, spmv_body, in eight forms)
+enum class SpmvFamily {
+    plain,            // csx_spmv_kernel: general path
+    accum,            // csx_spmv_accum_kernel: column slices in one launch, y tiles added with atomics
+    symtile,          // csx_spmv_symtile_kernel: symmetric tiles, sums spilled for csx_symfix_kernel
+    symtile_atomic,   // csx_spmv_symtile_atomic_kernel: ... handed over with global atomics
+    symseg,           // csx_spmv_symseg_kernel: ... and read-once row segments
+    symseg_notile,    // csx_spmv_symseg_notile_kernel: read-once row segments, no tiles
+    det,              // csx_spmv_det_kernel: a y tile per wavefront
+    symtile_det,      // csx_spmv_symtile_det_kernel: symmetric tiles, a copy of slots + y tile per wavefront
+};
+
+// spmv_kernels.hip (`waves`: 2, 4 or 8, anything else runs as 4; `stream`: a hipStream_t)
+void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a,
+                 const XcdSplit &xs);
+void spmv_allow_lds(SpmvFamily family, size_t bytes);      // dynamic LDS beyond the default 64 KB
+void launch_sym_init(void *stream, double *y, const double *x, const double *dvalues, size_t lo, size_t hi,
+                     size_t own_lo, size_t own_hi, double alpha, double beta);
+void launch_sym_mirror_rows(void *stream, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                            const double *val, const double *x, double *y, double alpha, uint32_t n);
+void launch_scale(void *stream, double *y, size_t lo, size_t hi, double beta);
+void launch_fixup(void *stream, const SpxSharedRow *shared, uint32_t n_shared, const double *carry, double *y,
+                  double alpha, double beta, const double *dvalues, const double *x);
+void launch_symfix(void *stream, const uint32_t *fix_ptr, const uint32_t *fix_idx, const double *spill, double *y,
+                   double alpha, size_t nrows);
+
+// spmv_sx_kernels.hip
+void launch_spmv_sx(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs,
+                    const uint32_t *sx_tab);
+size_t spmv_sx_header_bytes(uint32_t pass_stride);
+void spmv_sx_allow_lds(size_t bytes);
+
+// spmv_xw_kernels.hip
+void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs);
+void spmv_xw_allow_lds(size_t bytes);
+
+}  // namespace spx

@@ -1,5 +1,5 @@
 // spmv_sx_kernels.hip -- the symmetric read-once product with its passes software-pipelined
-// (csx_spmv_sx_kernel; device-side headers: sxplan.hpp; launched by device_spmv in spmv_kernels.hip for
+// (csx_spmv_sx_kernel; device-side headers: sxplan.hpp; launched by device_spmv in device_runtime.cpp for
 // streams of read-once row segments without tiles, where the launch tuner found it faster).
 //
 // Semantics as csx_spmv_symseg_notile_kernel's: the reference's symmetric SpMV template

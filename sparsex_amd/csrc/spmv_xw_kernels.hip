@@ -1,6 +1,6 @@
 // spmv_xw_kernels.hip -- the general-path product with the unit windows of x staged in LDS and the unit
 // passes software-pipelined (csx_spmv_xw_kernel; window plan: xwindows.hpp; launched by device_spmv in
-// spmv_kernels.hip where the launch tuner found it faster than the plain kernel).
+// device_runtime.cpp where the launch tuner found it faster than the plain kernel).
 //
 // Semantics as the plain kernel's: the reference's SpMV templates (src/templates/csx_spmv_tmpl.c:66-101,
 // horiz_tmpl.c:20-37, diag_tmpl.c:20-35, block_row_tmpl.c, block_col_tmpl.c), every stored nonzero a(r,c)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Host-side AddressSanitizer build of the library (CPU container only: the preprocessor, the
-# stream emitter, the index code and the C API are instrumented; the HIP objects are the regular
+# stream emitter, the index code, the C API and the host side of the device runtime -- upload,
+# launches, host-vector path, RCCL transport -- are instrumented; the HIP objects are the regular
 # ones).  Run the CPU tests against it:
 #   tools/build_asan.sh && LD_PRELOAD="$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libstdc++.so.6)" \
 #       ASAN_OPTIONS=detect_leaks=0 SPX_LIB_PATH=$PWD/sparsex_amd/lib/variants/libsparsex_asan.so \
@@ -17,7 +18,8 @@ HIPO=$(make -s -f Makefile print-hip-objs)
 rm -f build/asan/*.o
 for f in $HOST; do
     g++ -std=c++17 -O1 -g -fPIC -fsanitize=address,undefined -fno-omit-frame-pointer \
-        -Iinclude -Isparsex_amd/csrc -pthread -c sparsex_amd/csrc/$f -o build/asan/${f%.cpp}.o &
+        -Iinclude -Isparsex_amd/csrc -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
+        -c sparsex_amd/csrc/$f -o build/asan/${f%.cpp}.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o sparsex_amd/lib/variants/libsparsex_asan.so \

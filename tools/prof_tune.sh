@@ -9,7 +9,7 @@ CS=sparsex_amd/csrc
 # (the host sources and the HIP objects are the Makefile's lists)
 for src in $(make -s print-host-srcs); do
     f=${src%.cpp}
-    [ $O/$f.o -nt $CS/$f.cpp ] && [ -z "$(find $CS include -name "*.h*" -newer $O/$f.o)" ] || g++ -std=c++17 -O2 -g -fno-omit-frame-pointer -Iinclude -I$CS -pthread -c $CS/$f.cpp -o $O/$f.o
+    [ $O/$f.o -nt $CS/$f.cpp ] && [ -z "$(find $CS include -name "*.h*" -newer $O/$f.o)" ] || g++ -std=c++17 -O2 -g -fno-omit-frame-pointer -Iinclude -I$CS -pthread -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c $CS/$f.cpp -o $O/$f.o
 done
 gcc -O2 -g -pg -Iinclude -c tools/prof_tune.c -o $O/prof_tune.o
 gcc -O3 -c tools/synth/nlpkkt_gen.c -o $O/nlpkkt_gen.o
