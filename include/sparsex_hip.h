@@ -160,6 +160,28 @@ spx_error_t spx_hip_matvec_kernel(spx_value_t alpha, const spx_matrix_t *A,
                                   const spx_value_t *x_dev, spx_value_t beta,
                                   spx_value_t *y_dev, void *stream);
 
+/* ---- multi-vector product ----------------------------------------------------------
+ * Y <- alpha*A*X + beta*Y for nvec vectors at once, on device memory.
+ * Column-major blocks (BLAS convention): vector j of X is X_dev + j*ldx (ncols doubles, ldx >= ncols),
+ * vector j of Y is Y_dev + j*ldy (nrows doubles, ldy >= nrows).  HBM pointers on the matrix's device;
+ * enqueues only (hipGraph-capturable), like spx_hip_matvec_kernel.
+ * Column j of the result is what spx_hip_matvec_kernel(alpha, A, X_dev + j*ldx, beta, Y_dev + j*ldy, stream)
+ * writes: the same rows (row slices, an attached exchange plan), beta == 0 never reads Y, and with
+ * spx.gpu.deterministic=true every column is bit-identical to that product.  The padding between columns is
+ * never read or written; nvec == 0 does nothing.  SPX_FAILURE (through the error handler) for a NULL pointer
+ * with nvec > 0, ldx < ncols, ldy < nrows, overlapping X and Y, a host-only matrix or the wrong current device.
+ * One pass over the matrix' stream serves spx_hip_matmat_group(A) vectors (the values, descriptors and column
+ * offsets are read once for all of them); streams with symmetric tiles or read-once segments (the default
+ * symmetric tune) run one single-vector product per column -- exact, no faster: tune a symmetric matrix with
+ * spx.gpu.sym_once=false, or as a general one, for the multi-vector kernels.  Nothing is allocated.
+ */
+spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                  const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                  spx_value_t *Y_dev, size_t ldy, void *stream);
+/* Diagnostic: how many vectors one pass over this matrix' stream serves (>= 2: the multi-vector
+ * kernels run; 1: one product per vector), -1 for a matrix without a device copy. */
+int spx_hip_matmat_group(const spx_matrix_t *A);
+
 /* ---- device-resident vectors ---------------------------------------------------
  * HBM counterparts of the reference's host vector helpers (spx_vec_init,
  * spx_vec_scale, spx_vec_scale_add, spx_vec_add, spx_vec_sub, spx_vec_mul,

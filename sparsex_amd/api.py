@@ -264,6 +264,59 @@ class Matrix:
         if rc != SPX_SUCCESS:
             raise SpxError("spx_hip_matvec_kernel failed (see stderr)")
 
+    def hip_matmat_kernel(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
+        """``spx_hip_matmat_kernel``: Y <- alpha*A*X + beta*Y for nvec column-major vectors in HBM
+        (vector j of X at x_ptr + 8*j*ldx, of Y at y_ptr + 8*j*ldy)."""
+        L = lib()
+        L.spx_hip_matmat_kernel.restype = C.c_int
+        L.spx_hip_matmat_kernel.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                            C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+        rc = L.spx_hip_matmat_kernel(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
+        if rc != SPX_SUCCESS:
+            raise SpxError("spx_hip_matmat_kernel failed (see stderr)")
+
+    def matmat_group(self):
+        """``spx_hip_matmat_group``: vectors one pass over the stream serves (1: one product per vector;
+        -1: no device copy)."""
+        L = lib()
+        L.spx_hip_matmat_group.restype = C.c_int
+        L.spx_hip_matmat_group.argtypes = [C.c_void_p]
+        return int(L.spx_hip_matmat_group(C.c_void_p(self.handle)))
+
+    def matmat(self, alpha, X, beta, Y, stream=None):
+        """Y <- alpha*A*X + beta*Y for torch float64 tensors on the matrix' device: X of shape (nvec, ncols),
+        Y of shape (nvec, nrows), each row one vector, stride(1) == 1 and stride(0) the leading dimension.
+        `stream`: a torch stream (default: the current one of Y's device).  Returns Y."""
+        import torch
+        pairs = (("X", X, self.ncols), ("Y", Y, self.nrows))
+        for name, t, n in pairs:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a torch tensor" % name)
+            if t.dtype != torch.float64:
+                raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+            if t.dim() != 2 or t.shape[1] != n:
+                raise ValueError("%s must have the shape (nvec, %d), not %s" % (name, n, tuple(t.shape)))
+            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s needs stride(1) == 1, not %d" % (name, t.stride(1)))
+            if t.shape[0] > 1 and t.stride(0) < n:
+                raise ValueError("%s: stride(0) %d is below the vector length %d" % (name, t.stride(0), n))
+        if X.shape[0] != Y.shape[0]:
+            raise ValueError("X holds %d vectors, Y %d" % (X.shape[0], Y.shape[0]))
+        for name, t, n in pairs:
+            if t.device.type != "cuda":
+                raise ValueError("%s must live on the matrix' HIP device, not on %s" % (name, t.device))
+        if X.device != Y.device:
+            raise ValueError("X and Y live on different devices (%s, %s)" % (X.device, Y.device))
+        inf = self.info()
+        if inf.on_device and X.device.index != inf.device:
+            raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, X.device))
+        nvec = int(X.shape[0])
+        ldx = max(int(X.stride(0)), self.ncols) if nvec > 1 else max(self.ncols, 1)
+        ldy = max(int(Y.stride(0)), self.nrows) if nvec > 1 else max(self.nrows, 1)
+        st = stream if stream is not None else torch.cuda.current_stream(Y.device)
+        self.hip_matmat_kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
+        return Y
+
     def info(self):
         inf = HipInfo()
         if lib().spx_hip_mat_info(self.handle, C.byref(inf)) != SPX_SUCCESS:

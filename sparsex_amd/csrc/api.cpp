@@ -23,6 +23,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -2211,6 +2212,50 @@ try {
     }
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                  const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                  spx_value_t *Y_dev, size_t ldy, void *stream)
+try {
+    if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
+    if (!A->dev) {
+        SETERROR_1(SPX_ERR_TUNED_MAT,
+                   "matrix was tuned with spx.rt.host_only=true: no HIP executor");
+        return SPX_FAILURE;
+    }
+    if (nvec == 0) return SPX_SUCCESS;
+    if (!X_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid block X"); return SPX_FAILURE; }
+    if (!Y_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid block Y"); return SPX_FAILURE; }
+    const size_t nr = (size_t) A->nrows, nc = (size_t) A->ncols;
+    if (ldx < nc || ldy < nr) {
+        SETERROR_1(SPX_ERR_DIM, "leading dimension below the vector length (ldx >= ncols, ldy >= nrows)");
+        return SPX_FAILURE;
+    }
+    // the address ranges the two blocks span, first element to last, must not meet
+    const size_t limit = SIZE_MAX / sizeof(double);
+    if ((ldx && nvec - 1 > (limit - nc) / ldx) || (ldy && nvec - 1 > (limit - nr) / ldy)) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "block larger than the address space");
+        return SPX_FAILURE;
+    }
+    const uintptr_t x0 = (uintptr_t) X_dev, x1 = x0 + ((nvec - 1) * ldx + nc) * sizeof(double);
+    const uintptr_t y0 = (uintptr_t) Y_dev, y1 = y0 + ((nvec - 1) * ldy + nr) * sizeof(double);
+    if (x0 < y1 && y0 < x1) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "blocks X and Y overlap");
+        return SPX_FAILURE;
+    }
+    try {
+        device_spmm(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+int spx_hip_matmat_group(const spx_matrix_t *A)
+try {
+    return A && A->dev ? device_mv_group(A->dev) : -1;
+} SPX_C_BOUNDARY(return -1;)
 
 // ======================================================================================
 //  extensions: info / export

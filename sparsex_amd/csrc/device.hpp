@@ -28,6 +28,15 @@ void device_free(DeviceMatrix *m);
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream);
 
+// Y <- alpha*A*X + beta*Y for nvec vectors at once (column-major: vector j of X at d_X + j * ldx, of Y at
+// d_Y + j * ldy); column j is what device_spmv writes for it.  Groups of device_mv_group(m) vectors share one
+// pass over the stream (spmv_mv_kernels.hip); asynchronous on `stream`, no allocation.
+void device_spmm(DeviceMatrix *m, double alpha, const double *d_X, size_t ldx, size_t nvec, double beta,
+                 double *d_Y, size_t ldy, void *stream);
+// vectors per pass over the stream: 2, 4 or 8, or 1 (streams with symmetric tiles or read-once segments: one
+// single-vector product per column)
+int device_mv_group(const DeviceMatrix *m);
+
 // The product in K launches over consecutive parts of the row-blocks (equal work each), so that
 // the exchange of a row-partitioned matrix can start on the rows of part k while part k + 1 is
 // computed (dist.cpp).  Plain general streams only: device_plan_chunks returns 0 for the others;

@@ -34,6 +34,10 @@ struct DeviceMatrix {
     size_t init_lo = 0;       // symmetric slice with an exchange plan: first row to clear
     bool init_limited = false;   // ... and whether one is attached (spx_hip_mat_dist_attach)
     uint32_t n_rb = 0, n_shared = 0, n_carry = 0;
+    // the multi-vector product (device_spmm; streams without symmetric tiles or read-once segments): the carry of
+    // MV_MAX_GROUP vectors, the most rows and the longest x window of a row-block
+    double *carry_mv = nullptr;
+    uint32_t mv_rows = 0, mv_xwin = 0;
     SpxRowBlock *rbs = nullptr;
     double *values = nullptr;
     SpxUnitDesc *descs = nullptr;
@@ -141,6 +145,11 @@ struct DeviceMatrix {
     size_t xneed_piece = 0;
     hipStream_t up_stream = nullptr;            // ... on a stream of its own
 };
+
+// the multi-vector product (device_spmm): the widest group, and the LDS a workgroup of its kernels may take
+// (two of them fit a CU's 160 KB)
+constexpr int MV_MAX_GROUP = 8;
+constexpr size_t MV_LDS_BUDGET = (size_t) 80 << 10;
 
 // the host-vector entry point (device_spmv_host)
 constexpr size_t STAGE_PIECE = (size_t) 16 << 20;      // bytes
@@ -267,6 +276,14 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
         for (uint32_t k = 0; k < rb.n_pass && !m->has_tiles; ++k)
             m->has_tiles = s.passes[rb.pass_off + k].kind == SPX_PASS_SYMTILE ||
                            s.passes[rb.pass_off + k].kind == SPX_PASS_SYMSEG;
+    if (!m->has_tiles) {
+        for (const SpxRowBlock &rb : s.rbs) {
+            m->mv_rows = std::max<uint32_t>(m->mv_rows, rb.n_rows);
+            m->mv_xwin = std::max<uint32_t>(m->mv_xwin, rb.xwin_len);
+        }
+        place.put(&m->carry_mv, no_doubles, (size_t) MV_MAX_GROUP * (s.n_carry ? s.n_carry : 1));
+        spmv_mv_allow_lds(160u * 1024u);
+    }
     for (const SpxRowBlock &rb : s.rbs)
         for (uint32_t k = 0; k < rb.n_pass && !m->has_symsegs; ++k)
             m->has_symsegs = s.passes[rb.pass_off + k].kind == SPX_PASS_SYMSEG;
@@ -553,6 +570,7 @@ void device_free(DeviceMatrix *m)
         (void) hipFree(m->passes);
         (void) hipFree(m->cidx); (void) hipFree(m->segrows); (void) hipFree(m->shared);
         (void) hipFree(m->carry);
+        if (m->carry_mv) (void) hipFree(m->carry_mv);
         if (m->dvalues) (void) hipFree(m->dvalues);
         if (m->spill) (void) hipFree(m->spill);
         if (m->fix_ptr) (void) hipFree(m->fix_ptr);
@@ -729,6 +747,91 @@ static void device_spmv_impl(DeviceMatrix *m, double alpha, const double *d_x, d
     // value (beta*y, the diagonal term, its partial sums) from the fix-up kernel above, by a store
     if (need_symfix) launch_symfix(stream_, m->fix_ptr, m->fix_idx, m->spill, d_y, alpha, m->nrows);
     HIP_CHECK(hipGetLastError());
+}
+
+// ---- the multi-vector product ---------------------------------------------------------------------
+// Y <- alpha*A*X + beta*Y for nvec column-major vectors: groups of K vectors served by one pass over the plain
+// stream (spmv_mv_kernels.hip), in device_spmv_impl's launch order -- init / scale, the row-block launches of
+// every column phase, fix-up.  Streams with symmetric tiles or read-once segments, and a last vector on its
+// own, run the single-vector product: exact, column by column.
+
+// copies of the K tiles a workgroup keeps: one per wavefront where the single-vector product keeps one
+static size_t mv_copies(const DeviceMatrix *m) { return m->wave_tiles && !m->accum ? (size_t) m->waves : 1u; }
+
+// LDS of a workgroup of the K-vector kernels, with (stage) or without the K x windows
+static size_t mv_lds_bytes(const DeviceMatrix *m, int K, bool stage)
+{
+    return ((size_t) K * (mv_copies(m) * m->mv_rows + (stage ? m->mv_xwin : 0u))) * sizeof(double);
+}
+
+// the widest group whose y tiles fit MV_LDS_BUDGET (from the tune-time settings: row-blocks, waves, tiles per
+// wavefront); 1 where only the single-vector product runs
+int device_mv_group(const DeviceMatrix *m)
+{
+    if (m->has_tiles || !m->carry_mv) return 1;
+    for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
+        if (mv_lds_bytes(m, K, false) <= MV_LDS_BUDGET) return K;
+    return 1;
+}
+
+static void device_spmm_group(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
+                              size_t ldy, void *stream_)
+{
+    MvArgs a{};
+    a.rbs = m->rbs; a.passes = m->passes; a.values = m->values; a.descs = m->descs;
+    a.cidx = m->cidx; a.segrows = m->segrows; a.x = X; a.y = Y; a.ldx = ldx; a.ldy = ldy;
+    a.carry = m->carry_mv; a.n_carry = m->n_carry ? m->n_carry : 1u;
+    a.alpha = alpha; a.beta = beta;
+    a.pass_stride = m->pass_stride;
+    // (no tiles: no atomic hand-over either, so a fused symmetric stream adds its diagonal at the write-out)
+    const bool fused = m->sym_fused && !m->sym_atomic;
+    a.dvalues = fused ? m->dvalues : nullptr;
+    // the K x windows in LDS where they fit next to the tiles; else SPX_PASS_GATHER_LDS gathers through L2
+    a.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
+    const size_t lds = mv_lds_bytes(m, K, a.stage != 0);
+    if (m->symmetric && !fused) {
+        const size_t first = m->init_limited ? m->init_lo : 0, last = m->init_limited ? m->own_hi : m->nrows;
+        if (last > first) launch_mv_sym_init(stream_, K, Y, ldy, X, ldx, m->dvalues, first, last, m->own_lo, m->own_hi, alpha, beta);
+        if (m->n_mirror_rows)
+            launch_mv_sym_mirror_rows(stream_, K, m->mirror_rows, m->mirror_ptr, m->mirror_col, m->mirror_val, X, ldx, Y, ldy,
+                                      alpha, m->n_mirror_rows);
+        a.beta = beta = 1.0;
+    }
+    if (m->accum && !m->symmetric) {
+        if (m->own_hi > m->own_lo) launch_mv_scale(stream_, K, Y, ldy, m->own_lo, m->own_hi, beta);
+        a.beta = beta = 1.0;
+    }
+    const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
+    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
+        if (ph > 0) a.beta = 1.0;
+        const uint32_t blocks = 8u * m->xcd_longest[ph];
+        if (blocks) launch_spmv_mv(family, K, m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
+    }
+    if (m->n_shared)
+        launch_mv_fixup(stream_, K, m->shared, m->n_shared, m->carry_mv, a.n_carry, Y, ldy, alpha, beta, a.dvalues, X, ldx);
+    HIP_CHECK(hipGetLastError());
+}
+
+void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
+                 size_t ldy, void *stream_)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+    const int G = device_mv_group(m);
+    for (size_t j = 0; j < nvec;) {
+        int K = G;
+        while (K > 1 && (size_t) K > nvec - j) K /= 2;
+        if (K < 2) {
+            device_spmv_impl(m, alpha, X + j * ldx, beta, Y + j * ldy, stream_, nullptr);
+            ++j;
+            continue;
+        }
+        m->launched_since_edit = true;
+        device_spmm_group(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_);
+        j += (size_t) K;
+    }
 }
 
 // ---- the product in K launches over consecutive parts of the row-blocks ---------------------------

@@ -81,4 +81,43 @@ void spmv_sx_allow_lds(size_t bytes);
 void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs);
 void spmv_xw_allow_lds(size_t bytes);
 
+// spmv_mv_kernels.hip: the multi-vector product, K = 2, 4 or 8 vectors per pass over the plain stream.
+// Column-major blocks: vector j of X at x + j * ldx, of Y at y + j * ldy.
+struct MvArgs {
+    const SpxRowBlock *rbs;
+    const SpxPass *passes;
+    const double *values;
+    const SpxUnitDesc *descs;
+    const uint8_t *cidx;
+    const uint16_t *segrows;
+    const double *x;
+    double *y;
+    size_t ldx, ldy;
+    double *carry;             // SPX_RB_SHARED: vector j's partial of slot s at carry[j * n_carry + s]
+    const double *dvalues;     // symmetric, fused: diagonal added at the write-out (else null)
+    double alpha, beta;
+    uint32_t n_carry;
+    uint32_t pass_stride;
+    uint32_t stage;            // 1: the K x windows of a row-block are staged in LDS behind the K y tiles
+};
+enum class MvFamily {
+    plain,     // csx_spmv_mv_kernel: K y tiles per workgroup
+    accum,     // csx_spmv_mv_accum_kernel: column slices in one launch, tiles added with atomics
+    det,       // csx_spmv_mv_det_kernel: K y tiles per wavefront, summed in wavefront order
+};
+void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
+                    const XcdSplit &xs);
+void spmv_mv_allow_lds(size_t bytes);
+// the K-column forms of csx_fixup_kernel, csx_scale_kernel, csx_sym_init_kernel, csx_sym_mirror_rows_kernel
+void launch_mv_fixup(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
+                     uint32_t n_carry, double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                     const double *x, size_t ldx);
+void launch_mv_scale(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta);
+void launch_mv_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx,
+                        const double *dvalues, size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha,
+                        double beta);
+void launch_mv_sym_mirror_rows(void *stream, int nvec, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                               const double *val, const double *x, size_t ldx, double *y, size_t ldy, double alpha,
+                               uint32_t n);
+
 }  // namespace spx
