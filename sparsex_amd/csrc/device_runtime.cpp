@@ -605,14 +605,19 @@ struct SpmvPart {
     uint32_t longest;
     bool first, last;
 };
-static void device_spmv_impl(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_,
-                             const SpmvPart *part);
+static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
+                           size_t ldy, void *stream_, const SpmvPart *part);
 
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream_)
 {
-    device_spmv_impl(m, alpha, d_x, beta, d_y, stream_, nullptr);
+    device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, nullptr);
 }
+
+// (atomic hand-over of the tiles' sums: every row may be added to by several workgroups, so beta*y and the
+// diagonal term are put there first, as for a process that holds a slice; else a symmetric stream that holds
+// the whole matrix adds its diagonal at the write-out)
+static bool diagonal_at_writeout(const DeviceMatrix *m) { return m->sym_fused && !m->sym_atomic; }
 
 // the kernel arguments of a product (the symmetric path's first step changes beta; where the atomic hand-over
 // honours SPX_RB_PRIVATE, it sets dvalues_priv and beta_priv)
@@ -620,10 +625,10 @@ static KernelArgs kernel_args(const DeviceMatrix *m, double alpha, const double 
 {
     KernelArgs a{};
     a.rbs = m->rbs; a.values = m->values; a.descs = m->descs; a.passes = m->passes;
-    a.cidx = m->cidx; a.segrows = m->segrows; a.x = d_x; a.y = d_y;
+    a.cidx = m->cidx; a.segrows = m->segrows;                                         // (StreamArgs)
+    a.x = d_x; a.y = d_y; a.pass_stride = m->pass_stride;
     a.carry = m->carry; a.alpha = alpha; a.beta = beta; a.n_rb = m->n_rb;
-    a.dvalues = m->sym_fused && !m->sym_atomic ? m->dvalues : nullptr;     // (fused: at the write-out)
-    a.pass_stride = m->pass_stride;
+    a.dvalues = diagonal_at_writeout(m) ? m->dvalues : nullptr;
     a.slot_col = m->slot_col;
     a.spill = m->spill;
     return a;
@@ -677,83 +682,7 @@ static bool launch_rowblocks(const DeviceMatrix *m, const KernelArgs &a, const X
     return false;
 }
 
-static void device_spmv_impl(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_,
-                             const SpmvPart *part)
-{
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
-        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
-                         ", the calling thread's current device is " + std::to_string(cur));
-    m->launched_since_edit = true;
-    KernelArgs a = kernel_args(m, alpha, d_x, beta, d_y);
-    // (atomic hand-over of the tiles' sums: every row may be added to by several
-    // workgroups, so beta*y and the diagonal term are put there first, as for a
-    // process that holds a slice)
-    const bool fused = m->sym_fused && !m->sym_atomic;
-
-    const size_t n_launch = m->xcd_split.size();
-    if (m->symmetric && !fused) {
-        // y <- beta*y + alpha*diag*x on the owned rows, 0 elsewhere; the
-        // row-blocks (stored lower triangle and its mirror image) then
-        // accumulate on top of that
-        // (attached to an exchange plan: only [init_lo, own_hi) -- the rows this
-        // process owns or adds to -- are anybody's business)
-        const size_t first = m->init_limited ? m->init_lo : 0, last = m->init_limited ? m->own_hi : m->nrows;
-        auto init_rows = [&](size_t lo, size_t hi) {
-            if (hi > lo && !abl::sym_no_init && (!part || part->first))
-                launch_sym_init(stream_, d_y, d_x, m->dvalues, lo, hi, m->own_lo, m->own_hi, alpha, beta);
-        };
-        if (m->sym_atomic && !m->wave_tiles && m->use_private && !abl::sym_no_private) {
-            // (row-blocks that nobody else adds to store their rows themselves: SPX_RB_PRIVATE)
-            size_t at = first;
-            for (const auto &r : m->private_rows) {
-                if (r.second <= at) continue;
-                if (r.first >= last) break;
-                init_rows(at, std::min(std::max(r.first, at), last));
-                at = std::max(at, r.second);
-            }
-            init_rows(at, last);
-            a.dvalues_priv = m->dvalues;
-            a.beta_priv = beta;
-        }
-        else
-            init_rows(first, last);
-        // the thin mirror list stores its rows; whatever else lands on them (spilled tile
-        // sums) is added afterwards
-        if (m->n_mirror_rows && (!part || part->first))
-            launch_sym_mirror_rows(stream_, m->mirror_rows, m->mirror_ptr, m->mirror_col, m->mirror_val, d_x, d_y,
-                                   alpha, m->n_mirror_rows);
-        a.beta = beta = 1.0;
-    }
-    if (m->accum && !m->symmetric) {
-        // column slices in one launch: beta * y first, every row-block adds on top
-        const size_t lo = m->own_lo, hi = m->own_hi;
-        if (hi > lo) launch_scale(stream_, d_y, lo, hi, beta);
-        a.beta = beta = 1.0;
-    }
-    bool need_symfix = false;
-    for (size_t ph = 0; ph < n_launch; ++ph) {
-        // (column phases: slice k > 0 adds to what the slices in front of it stored)
-        if (ph > 0) a.beta = 1.0;
-        need_symfix |= launch_rowblocks(m, a, part ? part->split : m->xcd_split[ph],
-                                        8u * (part ? part->longest : m->xcd_longest[ph]), stream_);
-    }
-    if (part && !part->last) {
-        HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (m->n_shared) launch_fixup(stream_, m->shared, m->n_shared, m->carry, d_y, alpha, beta, a.dvalues, d_x);
-    // the spilled column sums are added last: a row that is split over several row-blocks gets its
-    // value (beta*y, the diagonal term, its partial sums) from the fix-up kernel above, by a store
-    if (need_symfix) launch_symfix(stream_, m->fix_ptr, m->fix_idx, m->spill, d_y, alpha, m->nrows);
-    HIP_CHECK(hipGetLastError());
-}
-
-// ---- the multi-vector product ---------------------------------------------------------------------
-// Y <- alpha*A*X + beta*Y for nvec column-major vectors: groups of K vectors served by one pass over the plain
-// stream (spmv_mv_kernels.hip), in device_spmv_impl's launch order -- init / scale, the row-block launches of
-// every column phase, fix-up.  Streams with symmetric tiles or read-once segments, and a last vector on its
-// own, run the single-vector product: exact, column by column.
+// ---- the multi-vector product: what its row-block launch needs -----------------------------------
 
 // copies of the K tiles a workgroup keeps: one per wavefront where the single-vector product keeps one
 static size_t mv_copies(const DeviceMatrix *m) { return m->wave_tiles && !m->accum ? (size_t) m->waves : 1u; }
@@ -774,62 +703,112 @@ int device_mv_group(const DeviceMatrix *m)
     return 1;
 }
 
-static void device_spmm_group(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
-                              size_t ldy, void *stream_)
+static uint32_t mv_n_carry(const DeviceMatrix *m) { return m->n_carry ? m->n_carry : 1u; }
+
+// launch_rowblocks for K >= 2 vectors: the plain stream through the kernels of spmv_mv_kernels.hip
+static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &a, size_t ldx, size_t ldy,
+                                const XcdSplit &xcd_now, uint32_t blocks, void *stream)
 {
-    MvArgs a{};
-    a.rbs = m->rbs; a.passes = m->passes; a.values = m->values; a.descs = m->descs;
-    a.cidx = m->cidx; a.segrows = m->segrows; a.x = X; a.y = Y; a.ldx = ldx; a.ldy = ldy;
-    a.carry = m->carry_mv; a.n_carry = m->n_carry ? m->n_carry : 1u;
-    a.alpha = alpha; a.beta = beta;
-    a.pass_stride = m->pass_stride;
-    // (no tiles: no atomic hand-over either, so a fused symmetric stream adds its diagonal at the write-out)
-    const bool fused = m->sym_fused && !m->sym_atomic;
-    a.dvalues = fused ? m->dvalues : nullptr;
+    if (!blocks) return;
+    MvArgs mv{};
+    static_cast<StreamArgs &>(mv) = a;
+    mv.x = a.x; mv.y = a.y; mv.ldx = ldx; mv.ldy = ldy;
+    mv.carry = m->carry_mv; mv.n_carry = mv_n_carry(m);
+    mv.dvalues = a.dvalues; mv.alpha = a.alpha; mv.beta = a.beta; mv.pass_stride = a.pass_stride;
     // the K x windows in LDS where they fit next to the tiles; else SPX_PASS_GATHER_LDS gathers through L2
-    a.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
-    const size_t lds = mv_lds_bytes(m, K, a.stage != 0);
-    if (m->symmetric && !fused) {
-        const size_t first = m->init_limited ? m->init_lo : 0, last = m->init_limited ? m->own_hi : m->nrows;
-        if (last > first) launch_mv_sym_init(stream_, K, Y, ldy, X, ldx, m->dvalues, first, last, m->own_lo, m->own_hi, alpha, beta);
-        if (m->n_mirror_rows)
-            launch_mv_sym_mirror_rows(stream_, K, m->mirror_rows, m->mirror_ptr, m->mirror_col, m->mirror_val, X, ldx, Y, ldy,
-                                      alpha, m->n_mirror_rows);
-        a.beta = beta = 1.0;
-    }
-    if (m->accum && !m->symmetric) {
-        if (m->own_hi > m->own_lo) launch_mv_scale(stream_, K, Y, ldy, m->own_lo, m->own_hi, beta);
-        a.beta = beta = 1.0;
-    }
+    mv.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
     const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
-    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
-        if (ph > 0) a.beta = 1.0;
-        const uint32_t blocks = 8u * m->xcd_longest[ph];
-        if (blocks) launch_spmv_mv(family, K, m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
-    }
-    if (m->n_shared)
-        launch_mv_fixup(stream_, K, m->shared, m->n_shared, m->carry_mv, a.n_carry, Y, ldy, alpha, beta, a.dvalues, X, ldx);
-    HIP_CHECK(hipGetLastError());
+    launch_spmv_mv(family, K, m->waves, blocks, mv_lds_bytes(m, K, mv.stage != 0), stream, mv, xcd_now);
 }
 
-void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
-                 size_t ldy, void *stream_)
+// Y <- alpha*A*X + beta*Y for K vectors (column-major: vector j of X at X + j * ldx, of Y at Y + j * ldy) in one
+// sequence of launches: init or scale, the row-blocks of every column phase, fix-up.  K == 1 runs the kernel that
+// the stream and the matrix' settings call for (launch_rowblocks), K = 2, 4, 8 (device_mv_group: streams without
+// symmetric tiles or read-once segments) the K-vector kernels over the plain stream.
+static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
+                           size_t ldy, void *stream_, const SpmvPart *part)
 {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
         throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
                          ", the calling thread's current device is " + std::to_string(cur));
+    m->launched_since_edit = true;
+    KernelArgs a = kernel_args(m, alpha, X, beta, Y);
+    const bool fused = diagonal_at_writeout(m);
+
+    const size_t n_launch = m->xcd_split.size();
+    if (m->symmetric && !fused) {
+        // y <- beta*y + alpha*diag*x on the owned rows, 0 elsewhere; the
+        // row-blocks (stored lower triangle and its mirror image) then
+        // accumulate on top of that
+        // (attached to an exchange plan: only [init_lo, own_hi) -- the rows this
+        // process owns or adds to -- are anybody's business)
+        const size_t first = m->init_limited ? m->init_lo : 0, last = m->init_limited ? m->own_hi : m->nrows;
+        auto init_rows = [&](size_t lo, size_t hi) {
+            if (hi > lo && !abl::sym_no_init && (!part || part->first))
+                launch_sym_init(stream_, K, Y, ldy, X, ldx, m->dvalues, lo, hi, m->own_lo, m->own_hi, alpha, beta);
+        };
+        if (K == 1 && m->sym_atomic && !m->wave_tiles && m->use_private && !abl::sym_no_private) {
+            // (row-blocks that nobody else adds to store their rows themselves: SPX_RB_PRIVATE)
+            size_t at = first;
+            for (const auto &r : m->private_rows) {
+                if (r.second <= at) continue;
+                if (r.first >= last) break;
+                init_rows(at, std::min(std::max(r.first, at), last));
+                at = std::max(at, r.second);
+            }
+            init_rows(at, last);
+            a.dvalues_priv = m->dvalues;
+            a.beta_priv = beta;
+        }
+        else
+            init_rows(first, last);
+        // the thin mirror list stores its rows; whatever else lands on them (spilled tile
+        // sums) is added afterwards
+        if (m->n_mirror_rows && (!part || part->first))
+            launch_sym_mirror_rows(stream_, K, m->mirror_rows, m->mirror_ptr, m->mirror_col, m->mirror_val, X, ldx, Y, ldy,
+                                   alpha, m->n_mirror_rows);
+        a.beta = beta = 1.0;
+    }
+    if (m->accum && !m->symmetric) {
+        // column slices in one launch: beta * y first, every row-block adds on top
+        const size_t lo = m->own_lo, hi = m->own_hi;
+        if (hi > lo) launch_scale(stream_, K, Y, ldy, lo, hi, beta);
+        a.beta = beta = 1.0;
+    }
+    bool need_symfix = false;
+    for (size_t ph = 0; ph < n_launch; ++ph) {
+        // (column phases: slice k > 0 adds to what the slices in front of it stored)
+        if (ph > 0) a.beta = 1.0;
+        const XcdSplit &split = part ? part->split : m->xcd_split[ph];
+        const uint32_t blocks = 8u * (part ? part->longest : m->xcd_longest[ph]);
+        if (K == 1) need_symfix |= launch_rowblocks(m, a, split, blocks, stream_);
+        else launch_rowblocks_mv(m, K, a, ldx, ldy, split, blocks, stream_);
+    }
+    if (part && !part->last) {
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    if (m->n_shared)
+        launch_fixup(stream_, K, m->shared, m->n_shared, K == 1 ? m->carry : m->carry_mv, mv_n_carry(m), Y, ldy, alpha,
+                     beta, a.dvalues, X, ldx);
+    // the spilled column sums are added last: a row that is split over several row-blocks gets its
+    // value (beta*y, the diagonal term, its partial sums) from the fix-up kernel above, by a store
+    if (need_symfix) launch_symfix(stream_, m->fix_ptr, m->fix_idx, m->spill, Y, alpha, m->nrows);
+    HIP_CHECK(hipGetLastError());
+}
+
+// Y <- alpha*A*X + beta*Y for nvec column-major vectors: groups of K vectors served by one pass over the plain
+// stream.  Streams with symmetric tiles or read-once segments, and a last vector on its own, run the
+// single-vector product: exact, column by column.
+void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
+                 size_t ldy, void *stream_)
+{
     const int G = device_mv_group(m);
     for (size_t j = 0; j < nvec;) {
         int K = G;
         while (K > 1 && (size_t) K > nvec - j) K /= 2;
-        if (K < 2) {
-            device_spmv_impl(m, alpha, X + j * ldx, beta, Y + j * ldy, stream_, nullptr);
-            ++j;
-            continue;
-        }
-        m->launched_since_edit = true;
-        device_spmm_group(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_);
+        device_product(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_, nullptr);
         j += (size_t) K;
     }
 }
@@ -984,10 +963,10 @@ void device_spmv_chunk(DeviceMatrix *m, size_t k, double alpha, const double *d_
         const bool last = position < 0 ? k + 1 == cp.split.size() : (position & 2) != 0;
         if (last && cp.front_longest) {
             SpmvPart front{cp.front, cp.front_longest, false, false};
-            device_spmv_impl(m, alpha, d_x, beta, d_y, stream_, &front);
+            device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, &front);
         }
         SpmvPart part{xs, cp.longest[k], first, last};
-        device_spmv_impl(m, alpha, d_x, beta, d_y, stream_, &part);
+        device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, &part);
         return;
     }
     if (!blocks) return;

@@ -120,10 +120,8 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
                 else run_pass(a, rb, p1, tile, win, lane);
             }
         } else if (two) {
-            if (p0.kind == p1.kind && p0.width == p1.width) {
-                if (p0.kind == SPX_PASS_GATHER) run_units<2, 1>(a, rb, {p0, p1}, tile, win, lane);
-                else if (p0.kind == SPX_PASS_GATHER_LDS) run_units<2, 2>(a, rb, {p0, p1}, tile, win, lane);
-                else run_units<2, 0>(a, rb, {p0, p1}, tile, win, lane);
+            if (same_shape(p0, p1)) {
+                run_pair(a, rb, {p0, p1}, tile, win, lane);
             } else {
                 run_pass(a, rb, p0, tile, win, lane);
                 if (SYM && TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
@@ -187,7 +185,10 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
 }
 
 
-// (Individual scalar arguments, most urgent first.  Preloading them into SGPRs
+// (Individual scalar arguments, most urgent first, where the K-vector kernels take their MvArgs as one
+// struct: these kernels are tuned to the register and to the order in which their arguments arrive, so the
+// stream pointers that the two share (StreamArgs) are filled in one place on the host and spread here.
+// Preloading them into SGPRs
 // at wave launch -- hipcc -mllvm -amdgpu-kernarg-preload-count=16 -- was
 // measured: it removes the kernarg fetch in front of the first real load but
 // costs more at dispatch, cant 7.5 -> 8.0 us; not used.)
@@ -300,55 +301,63 @@ void csx_symfix_kernel(const uint32_t *fix_ptr, const uint32_t *fix_idx,
     if (g == 0 && row < nrows && s != 0.0) y[row] += alpha * s;
 }
 
-// rows split over several row-blocks: sum their partials
-__global__ void csx_fixup_kernel(const SpxSharedRow *shared, uint32_t n_shared,
-                                 const double *carry, double *y, double alpha,
-                                 double beta, const double *dvalues, const double *x)
+// ---- the steps around the row-block launches, for gridDim.y vectors at once (blockIdx.y: the vector; vector j
+// of x at x + j * ldx, of y at y + j * ldy) ------------------------------------------------------------------
+
+// rows split over several row-blocks: sum their partials (vector j's at carry + j * n_carry)
+__global__ void csx_fixup_kernel(const SpxSharedRow *shared, uint32_t n_shared, const double *carry, uint32_t n_carry,
+                                 double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                                 const double *x, size_t ldx)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_shared) return;
+    const size_t j = blockIdx.y;
     const SpxSharedRow sr = shared[i];
-    double s = dvalues ? dvalues[sr.row] * x[sr.row] : 0.0;
-    for (uint32_t k = 0; k < sr.n_slots; ++k) s += carry[sr.first_slot + k];
-    y[sr.row] = (beta == 0.0) ? alpha * s : alpha * s + beta * y[sr.row];
+    const double *cj = carry + j * n_carry;
+    double *yj = y + j * ldy;
+    double s = dvalues ? dvalues[sr.row] * x[j * ldx + sr.row] : 0.0;
+    for (uint32_t k = 0; k < sr.n_slots; ++k) s += cj[sr.first_slot + k];
+    yj[sr.row] = (beta == 0.0) ? alpha * s : alpha * s + beta * yj[sr.row];
 }
 
 // column slices in one launch, first step: y <- beta * y on the rows [lo, hi)
-__global__ void csx_scale_kernel(double *y, size_t lo, size_t hi, double beta)
+__global__ void csx_scale_kernel(double *y, size_t ldy, size_t lo, size_t hi, double beta)
 {
     const size_t i = lo + (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < hi) y[i] = beta == 0.0 ? 0.0 : beta * y[i];
+    double *yj = y + (size_t) blockIdx.y * ldy;
+    if (i < hi) yj[i] = beta == 0.0 ? 0.0 : beta * yj[i];
 }
 
 // symmetric path, first step: y <- beta*y + alpha*diag(A)*x on the owned
 // rows, 0 elsewhere (the main kernel then accumulates; on several GPUs the
 // per-GPU vectors are summed afterwards)
-__global__ void csx_sym_init_kernel(double *y, const double *x, const double *dvalues,
-                                    size_t first, size_t nrows, size_t own_lo, size_t own_hi,
-                                    double alpha, double beta)
+__global__ void csx_sym_init_kernel(double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
+                                    size_t first, size_t nrows, size_t own_lo, size_t own_hi, double alpha, double beta)
 {
     const size_t i = first + (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nrows) return;
+    double *yj = y + (size_t) blockIdx.y * ldy;
     double v = 0.0;
     if (i >= own_lo && i < own_hi) {
-        v = alpha * dvalues[i] * x[i];
-        if (beta != 0.0) v += beta * y[i];
+        v = alpha * dvalues[i] * x[(size_t) blockIdx.y * ldx + i];
+        if (beta != 0.0) v += beta * yj[i];
     }
-    y[i] = v;
+    yj[i] = v;
 }
 
 // symmetric slice: the thinly spread part of the mirror image on rows of other
 // processes (GpuStream::mirror_*): one thread per such row, its few nonzeros in
 // fixed order.  The rows are distinct and no row-block touches them.
 __global__ void csx_sym_mirror_rows_kernel(const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
-                                           const double *val, const double *x, double *y, double alpha,
-                                           uint32_t n)
+                                           const double *val, const double *x, size_t ldx, double *y, size_t ldy,
+                                           double alpha, uint32_t n)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
+    const double *xj = x + (size_t) blockIdx.y * ldx;
     double s = 0.0;
-    for (uint32_t k = ptr[t]; k < ptr[t + 1]; ++k) s = fma(val[k], x[col[k]], s);
-    y[rows[t]] = alpha * s;          // (nothing else adds to these rows: no need to clear them first)
+    for (uint32_t k = ptr[t]; k < ptr[t + 1]; ++k) s = fma(val[k], xj[col[k]], s);
+    y[(size_t) blockIdx.y * ldy + rows[t]] = alpha * s;          // (nothing else adds to these rows: no need to clear them first)
 }
 
 // ---- launchers ------------------------------------------------------------------------------
@@ -388,33 +397,36 @@ void spmv_allow_lds(SpmvFamily family, size_t bytes)
         (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b);
 }
 
-void launch_sym_init(void *stream, double *y, const double *x, const double *dvalues, size_t lo, size_t hi,
-                     size_t own_lo, size_t own_hi, double alpha, double beta)
+void launch_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
+                     size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha, double beta)
 {
     const int t = 256;
-    hipLaunchKernelGGL(csx_sym_init_kernel, dim3((unsigned)((hi - lo + t - 1) / t)), dim3(t), 0,
-                       static_cast<hipStream_t>(stream), y, x, dvalues, lo, hi, own_lo, own_hi, alpha, beta);
+    hipLaunchKernelGGL(csx_sym_init_kernel, dim3((unsigned)((hi - lo + t - 1) / t), (unsigned) nvec), dim3(t), 0,
+                       static_cast<hipStream_t>(stream), y, ldy, x, ldx, dvalues, lo, hi, own_lo, own_hi, alpha, beta);
 }
 
-void launch_sym_mirror_rows(void *stream, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
-                            const double *val, const double *x, double *y, double alpha, uint32_t n)
+void launch_sym_mirror_rows(void *stream, int nvec, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                            const double *val, const double *x, size_t ldx, double *y, size_t ldy, double alpha,
+                            uint32_t n)
 {
-    hipLaunchKernelGGL(csx_sym_mirror_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       rows, ptr, col, val, x, y, alpha, n);
+    hipLaunchKernelGGL(csx_sym_mirror_rows_kernel, dim3((n + 255) / 256, (unsigned) nvec), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), rows, ptr, col, val, x, ldx, y, ldy, alpha, n);
 }
 
-void launch_scale(void *stream, double *y, size_t lo, size_t hi, double beta)
+void launch_scale(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta)
 {
     const int t = 256;
-    hipLaunchKernelGGL(csx_scale_kernel, dim3((unsigned)((hi - lo + t - 1) / t)), dim3(t), 0,
-                       static_cast<hipStream_t>(stream), y, lo, hi, beta);
+    hipLaunchKernelGGL(csx_scale_kernel, dim3((unsigned)((hi - lo + t - 1) / t), (unsigned) nvec), dim3(t), 0,
+                       static_cast<hipStream_t>(stream), y, ldy, lo, hi, beta);
 }
 
-void launch_fixup(void *stream, const SpxSharedRow *shared, uint32_t n_shared, const double *carry, double *y,
-                  double alpha, double beta, const double *dvalues, const double *x)
+void launch_fixup(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
+                  uint32_t n_carry, double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                  const double *x, size_t ldx)
 {
-    hipLaunchKernelGGL(csx_fixup_kernel, dim3((n_shared + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       shared, n_shared, carry, y, alpha, beta, dvalues, x);
+    hipLaunchKernelGGL(csx_fixup_kernel, dim3((n_shared + 63) / 64, (unsigned) nvec), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), shared, n_shared, carry, n_carry, y, ldy, alpha, beta, dvalues,
+                       x, ldx);
 }
 
 // (four wavefronts of eight rows per workgroup; a multiple of eight workgroups, one share per XCD)

@@ -1,7 +1,7 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the three interpreter translation
-// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip).  Plain C++: no HIP header, so that
-// the host runtime (device_runtime.cpp) is compiled by the host compiler.
+// XCD-aware row-block order, the kernel families and the launchers of the four interpreter translation
+// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_mv_kernels.hip).  Plain C++: no
+// HIP header, so that the host runtime (device_runtime.cpp) is compiled by the host compiler.
 #pragma once
 
 #include "gpu_format.h"
@@ -12,13 +12,21 @@
 
 namespace spx {
 
-struct KernelArgs {
+// the stream of a matrix on the device: what every kernel that walks row-blocks reads, whatever it multiplies with.
+// (The K-vector kernels take their arguments as one struct, and the order of its fields decides how they
+// arrive in SGPRs: with pass_stride in here, in front of x, the K = 8 kernels spilled 215 SGPRs where they
+// spill 92 -- profiles/r08/REFACTOR.md.  So it stays where each struct had it.)
+struct StreamArgs {
     const SpxRowBlock *rbs;
     const SpxPass *passes;
     const double *values;
     const SpxUnitDesc *descs;
     const uint8_t *cidx;
     const uint16_t *segrows;
+};
+
+// the single-vector kernels
+struct KernelArgs : StreamArgs {
     const double *x;
     double *y;
     double *carry;
@@ -61,13 +69,17 @@ enum class SpmvFamily {
 void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a,
                  const XcdSplit &xs);
 void spmv_allow_lds(SpmvFamily family, size_t bytes);      // dynamic LDS beyond the default 64 KB
-void launch_sym_init(void *stream, double *y, const double *x, const double *dvalues, size_t lo, size_t hi,
-                     size_t own_lo, size_t own_hi, double alpha, double beta);
-void launch_sym_mirror_rows(void *stream, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
-                            const double *val, const double *x, double *y, double alpha, uint32_t n);
-void launch_scale(void *stream, double *y, size_t lo, size_t hi, double beta);
-void launch_fixup(void *stream, const SpxSharedRow *shared, uint32_t n_shared, const double *carry, double *y,
-                  double alpha, double beta, const double *dvalues, const double *x);
+// the steps around the row-block launches, for `nvec` vectors at once (gridDim.y; vector j of x at x + j * ldx,
+// of y at y + j * ldy, its carry slots at carry + j * n_carry)
+void launch_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
+                     size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha, double beta);
+void launch_sym_mirror_rows(void *stream, int nvec, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                            const double *val, const double *x, size_t ldx, double *y, size_t ldy, double alpha,
+                            uint32_t n);
+void launch_scale(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta);
+void launch_fixup(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
+                  uint32_t n_carry, double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                  const double *x, size_t ldx);
 void launch_symfix(void *stream, const uint32_t *fix_ptr, const uint32_t *fix_idx, const double *spill, double *y,
                    double alpha, size_t nrows);
 
@@ -83,13 +95,7 @@ void spmv_xw_allow_lds(size_t bytes);
 
 // spmv_mv_kernels.hip: the multi-vector product, K = 2, 4 or 8 vectors per pass over the plain stream.
 // Column-major blocks: vector j of X at x + j * ldx, of Y at y + j * ldy.
-struct MvArgs {
-    const SpxRowBlock *rbs;
-    const SpxPass *passes;
-    const double *values;
-    const SpxUnitDesc *descs;
-    const uint8_t *cidx;
-    const uint16_t *segrows;
+struct MvArgs : StreamArgs {
     const double *x;
     double *y;
     size_t ldx, ldy;
@@ -108,16 +114,5 @@ enum class MvFamily {
 void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
                     const XcdSplit &xs);
 void spmv_mv_allow_lds(size_t bytes);
-// the K-column forms of csx_fixup_kernel, csx_scale_kernel, csx_sym_init_kernel, csx_sym_mirror_rows_kernel
-void launch_mv_fixup(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
-                     uint32_t n_carry, double *y, size_t ldy, double alpha, double beta, const double *dvalues,
-                     const double *x, size_t ldx);
-void launch_mv_scale(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta);
-void launch_mv_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx,
-                        const double *dvalues, size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha,
-                        double beta);
-void launch_mv_sym_mirror_rows(void *stream, int nvec, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
-                               const double *val, const double *x, size_t ldx, double *y, size_t ldy, double alpha,
-                               uint32_t n);
 
 }  // namespace spx

@@ -220,14 +220,9 @@ __device__ __forceinline__ void symseg_passes(const KernelArgs &a, const SpxRowB
     double xr[B], x[B][W];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
-        const uint32_t bits = q[b].y;
-        const int s = (int) ((ps[b].seg0 + l[b] - ((bits >> 9) & 8191u)) & 0xffffu);
-        const uint32_t kind = (bits >> 22) & 7u;
-        const int step = (int) (bits >> 25);
-        const int drow = kind == SPX_KIND_BLOCK ? 1 : (kind >= SPX_KIND_VERT ? step : 0);
-        const int dcol = (kind == SPX_KIND_HORIZ || kind == SPX_KIND_DIAG) ? step : (kind == SPX_KIND_ADIAG ? -step : 0);
-        row[b] = (int) (ps[b].elem0 + (bits & 511u)) + s * drow;
-        sdc[b] = s * dcol;
+        const UnitOrigin o = unit_origin(q[b].y, ps[b].seg0 + l[b], ps[b].elem0);
+        row[b] = o.row;
+        sdc[b] = o.dcol;
         col[b] = q[b].x + (uint32_t) sdc[b];
         const double *xp = a.x + col[b];
         // (x in unaligned pairs, as the unit passes load it, measured 2.3 % slower here: one load per column)

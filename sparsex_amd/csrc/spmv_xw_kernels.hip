@@ -16,7 +16,7 @@ namespace spx {
 
 // ---- general path, unit windows of x in LDS, unit passes software-pipelined ------------------------
 //
-// What the plain kernel above leaves on the table on a large streaming matrix (profiles/r04/spread.md:
+// What the plain kernel (spmv_kernels.hip) leaves on the table on a large streaming matrix (profiles/r04/spread.md:
 // the bare read probe holds 5.9 TB/s on every node, this product swings by 16 % with the node): a
 // wavefront runs header -> {values, x} -> FMAs -> LDS adds strictly in turn, so between two passes it has
 // nothing in flight, and every pass pushes as many bytes of x through the vector L1 as it reads values.
@@ -81,15 +81,9 @@ template <int W>
 __device__ __forceinline__ void xw_finish_pass(uint2 q, uint32_t segl, uint32_t row0, spx_d2u_t va, spx_d2u_t vb,
                                                double *tile, const double *xw)
 {
-    const uint32_t c0 = q.x, bits = q.y;
-    const int s = (int) ((segl - ((bits >> 9) & 8191u)) & 0xffffu);
-    const uint32_t kind = (bits >> 22) & 7u;
-    const int step = (int) (bits >> 25);
-    const int drow = kind == SPX_KIND_BLOCK ? 1 : (kind >= SPX_KIND_VERT ? step : 0);
-    const int dcol = (kind == SPX_KIND_HORIZ || kind == SPX_KIND_DIAG)
-                         ? step : (kind == SPX_KIND_ADIAG ? -step : 0);
-    const int row = (int) (row0 + (bits & 511u)) + s * drow;
-    const double *xp = xw + (int) (c0 + (uint32_t) (s * dcol));      // (c0: an offset into the unit windows)
+    const UnitOrigin o = unit_origin(q.y, segl, row0);
+    const int row = o.row;
+    const double *xp = xw + (int) (q.x + (uint32_t) o.dcol);         // (q.x: an offset into the unit windows)
     double t = va.x * xp[0];
     if (W >= 2) t = fma(va.y, xp[1], t);
     if (W >= 3) t = fma(vb.x, xp[2], t);
@@ -129,14 +123,9 @@ __device__ __forceinline__ void xw_wide(const KernelArgs &a, const SpxRowBlock &
     for (int p = 0; p < W / 2; ++p)
         v2[p] = ld_stream(reinterpret_cast<const double2 *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
     if (W & 1) v1 = ld_stream(vals + (uint32_t) (W / 2) * 2u * nseg + l);
-    const uint32_t bits = q.y;
-    const int s = (int) ((ps.seg0() + l - ((bits >> 9) & 8191u)) & 0xffffu);
-    const uint32_t kind = (bits >> 22) & 7u;
-    const int step = (int) (bits >> 25);
-    const int drow = kind == SPX_KIND_BLOCK ? 1 : (kind >= SPX_KIND_VERT ? step : 0);
-    const int dcol = (kind == SPX_KIND_HORIZ || kind == SPX_KIND_DIAG) ? step : (kind == SPX_KIND_ADIAG ? -step : 0);
-    const int row = (int) (ps.w[5] + (bits & 511u)) + s * drow;
-    const double *xp = xw + (int) (q.x + (uint32_t) (s * dcol));
+    const UnitOrigin o = unit_origin(q.y, ps.seg0() + l, ps.w[5]);
+    const int row = o.row;
+    const double *xp = xw + (int) (q.x + (uint32_t) o.dcol);
     double t = 0.0;
 #pragma unroll
     for (int p = 0; p < W / 2; ++p) {

@@ -1,17 +1,26 @@
 #!/bin/bash
-# Registers, scratch and LDS of every kernel of spmv_kernels.hip (cross-compiled, no GPU needed):
+# Registers, scratch and LDS of every kernel of the interpreter's translation units (cross-compiled, no GPU
+# needed):
 #   tools/kernel_regs.sh [pattern] [extra hipcc flags]
-# leaves the assembly in /tmp/spx_asm/spmv.s
+# SPX_TU: the units, default all four ("spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_mv_kernels"; any
+# other .hip file of sparsex_amd/csrc works too).  They compile side by side and leave their assembly in
+# /tmp/spx_asm/<unit>.s
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p /tmp/spx_asm
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -munsafe-fp-atomics -Iinclude -Isparsex_amd/csrc \
-    ${2:-} -S --cuda-device-only -o /tmp/spx_asm/spmv.s sparsex_amd/csrc/${SPX_TU:-spmv_kernels}.hip 2>/dev/null
-python3 - "${1:-.}" <<'PY'
+units=${SPX_TU:-spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_mv_kernels}
+for tu in $units; do
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -munsafe-fp-atomics -Iinclude -Isparsex_amd/csrc \
+        ${2:-} -S --cuda-device-only -o /tmp/spx_asm/$tu.s sparsex_amd/csrc/$tu.hip 2>/dev/null &
+done
+wait
+for tu in $units; do
+python3 - "${1:-.}" "$tu" <<'PY'
 import re, sys
 pat = re.compile(sys.argv[1])
+print("# %s" % sys.argv[2])
 cur = {}
-for line in open("/tmp/spx_asm/spmv.s"):
+for line in open("/tmp/spx_asm/%s.s" % sys.argv[2]):
     m = re.match(r"\s+\.(name|sgpr_count|vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|agpr_count):\s+(\S+)", line)
     if not m:
         continue
@@ -25,3 +34,4 @@ for line in open("/tmp/spx_asm/spmv.s"):
             name, cur.get("vgpr_count"), cur.get("sgpr_count"), cur.get("private_segment_fixed_size", "?"),
             cur.get("vgpr_spill_count"), cur.get("sgpr_spill_count", "?")))
 PY
+done
