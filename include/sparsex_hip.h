@@ -189,7 +189,10 @@ int spx_hip_matmat_group(const spx_matrix_t *A);
  * Vector.cpp:206-394) so that a CG / GMRES iteration never leaves the GPU.
  * Same argument order and meaning as the host versions; every call enqueues on
  * `stream` (NULL = default stream) and returns immediately, except
- * spx_hip_vec_mul and the download, which synchronise the stream.
+ * spx_hip_vec_mul and the download, which synchronise the stream.  A solver
+ * loop that must not stall (or that is captured into a hipGraph) keeps its
+ * scalars in HBM instead: spx_hip_vec_mul_dev, spx_hip_vec_scale_add_ratio and
+ * spx_hip_vec_cg_update below take and leave them there, and only enqueue.
  */
 typedef struct spx_hip_vec spx_hip_vec_t;
 
@@ -224,6 +227,25 @@ spx_error_t spx_hip_vec_sub(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2,
 spx_error_t spx_hip_vec_mul(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2,
                             spx_value_t *result, void *stream);
 spx_error_t spx_hip_vec_copy(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, void *stream);
+/* ---- device scalars: a spx_value_t in HBM, given by pointer (typically an element of a small spx_hip_vec_t,
+ * spx_hip_vec_data(s) + i).  The three calls below only enqueue: no allocation, no copy to the host, no
+ * synchronisation; all are legal during stream capture.  A scalar may not lie inside a vector the call writes. */
+/* *result_dev <- v1 . v2, the bits spx_hip_vec_mul returns (same grid, same partial sums, same order) */
+spx_error_t spx_hip_vec_mul_dev(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2,
+                                spx_value_t *result_dev, void *stream);
+/* v3 <- v1 + c * v2,  c = scale * (*num_dev / *den_dev): what spx_hip_vec_scale_add gives for that host value.
+ * den_dev == NULL: c = scale * *num_dev;  *den_dev == 0: c = 0.  v3 may be v1 or v2. */
+spx_error_t spx_hip_vec_scale_add_ratio(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, spx_hip_vec_t *v3,
+                                        spx_value_t scale, const spx_value_t *num_dev,
+                                        const spx_value_t *den_dev, void *stream);
+/* One CG update in one pass over the vectors:  a = *rr_dev / *pap_dev (0 if *pap_dev == 0);
+ *   x += a*p;  r -= a*ap;  rr_new = r.r (fixed order: reproducible; not the bits of spx_hip_vec_mul(r, r));
+ *   *beta_dev = rr_new / *rr_dev (0 if *rr_dev == 0);  *rr_dev = rr_new.
+ * x and r are what two spx_hip_vec_scale_add calls with a and -a give.  x, p, r, ap: four different vectors;
+ * rr_dev, pap_dev, beta_dev: three different addresses.  With r = p = 0 the call changes nothing (no NaN). */
+spx_error_t spx_hip_vec_cg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_hip_vec_t *r,
+                                  const spx_hip_vec_t *ap, spx_value_t *rr_dev,
+                                  const spx_value_t *pap_dev, spx_value_t *beta_dev, void *stream);
 /* Diagnostic: a read stream with the stores of an SpMV in it.  `src` is read in chunks of `chunk_doubles` (a
  * multiple of 2048), one per workgroup, workgroup b on XCD b % 8 as the SpMV kernels' row-blocks; every workgroup
  * then stores `write_doubles` doubles to its stretch of `dst` (dst->size >= chunks * write_doubles).  Timed by

@@ -149,6 +149,9 @@ def lib():
     L.spx_hip_vec_sub.argtypes = [vp, vp, vp, vp]
     L.spx_hip_vec_mul.argtypes = [vp, vp, C.POINTER(C.c_double), vp]
     L.spx_hip_vec_copy.argtypes = [vp, vp, vp]
+    L.spx_hip_vec_mul_dev.argtypes = [vp, vp, vp, vp]
+    L.spx_hip_vec_scale_add_ratio.argtypes = [vp, vp, vp, d, vp, vp, vp]
+    L.spx_hip_vec_cg_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.spx_hip_matvec_kernel_vec.argtypes = [d, vp, vp, d, vp, vp]
     L.spx_log_disable_all.restype = None
     L.spx_log_error_console.restype = None
@@ -526,6 +529,23 @@ class DeviceVector:
                     "spx_hip_vec_mul")
         return r.value
 
+    def slot_ptr(self, index=0):
+        """HBM address of element `index`: a device scalar for dot_into, scale_add_ratio_into and cg_update."""
+        if not 0 <= index < self.size:
+            raise SpxError("device scalar index %d outside a vector of %d" % (index, self.size))
+        return self.data_ptr() + 8 * index
+
+    def dot_into(self, other, out, index=0, stream=0):     # out[index] <- self . other, nothing leaves the GPU
+        self._check(lib().spx_hip_vec_mul_dev(self.handle, other.handle, out.slot_ptr(index), stream),
+                    "spx_hip_vec_mul_dev")
+
+    def scale_add_ratio_into(self, other, dst, scale, num, den=None, stream=0):
+        """dst <- self + scale * (num / den) * other; num, den: (DeviceVector, index) pairs, den=None: no division."""
+        nump = num[0].slot_ptr(num[1]) if num is not None else None
+        denp = den[0].slot_ptr(den[1]) if den is not None else None
+        self._check(lib().spx_hip_vec_scale_add_ratio(self.handle, other.handle, dst.handle, scale, nump, denp,
+                                                      stream), "spx_hip_vec_scale_add_ratio")
+
     def probe_read_write(self, dst, chunk_doubles, write_doubles, stream=0):
         """Diagnostic (spx_hip_probe_read_write): this vector read in chunks, `write_doubles` stored per chunk to dst."""
         L = lib()
@@ -553,6 +573,15 @@ def matvec_kernel_vec(A, alpha, x, beta, y, stream=0):
     rc = lib().spx_hip_matvec_kernel_vec(alpha, A.handle, x.handle, beta, y.handle, stream)
     if rc != SPX_SUCCESS:
         raise SpxError("spx_hip_matvec_kernel_vec failed (see stderr)")
+
+
+def cg_update(x, p, r, ap, scalars, stream=0):
+    """``spx_hip_vec_cg_update``: x += a p, r -= a ap, a = rr / pap; then beta = r.r / rr and rr = r.r.
+    `scalars` is a DeviceVector holding rr, pap, beta in its elements 0, 1, 2; it may be None (an error of the call)."""
+    sp = [scalars.slot_ptr(k) if scalars is not None else None for k in range(3)]
+    rc = lib().spx_hip_vec_cg_update(x.handle, p.handle, r.handle, ap.handle, sp[0], sp[1], sp[2], stream)
+    if rc != SPX_SUCCESS:
+        raise SpxError("spx_hip_vec_cg_update failed (see stderr)")
 
 
 def mat_restore(filename):

@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdlib>
 #include <string>
 
@@ -34,6 +35,7 @@ namespace {
 constexpr int VEC_BLOCK = 256;
 constexpr unsigned VEC_CHUNK_MAX = 4096;  // double2 per workgroup and operand: 64 KB (the dot product: reads only)
 constexpr unsigned VEC_CHUNK_MAP = 1024;  // ... 16 KB: four accesses per lane (kernels that write; measured best, tools/vec_bench.py)
+constexpr unsigned VEC_CHUNK_CG = 4096;   // ... the fused CG update, four streams in and two out: 64 KB (2 % over 16 KB at 28 M doubles, profiles/r09/CG_STEP.md)
 constexpr unsigned VEC_CHUNK_MIN = 1024;
 constexpr unsigned VEC_DOT_BLOCKS = 4096; // most workgroups of the dot product (each ends with a store)
 constexpr unsigned VEC_MIN_BLOCKS = 2048; // a vector is cut finely enough for eight workgroups per CU where it is long enough
@@ -81,10 +83,9 @@ __device__ __forceinline__ double2 vec_map_one(double2 va, double2 vb, double s)
 }
 
 template <int KIND>
-__global__ __launch_bounds__(VEC_BLOCK) void vec_map_kernel(double *__restrict__ d,
-                                                            const double *__restrict__ a,
-                                                            const double *__restrict__ b,
-                                                            double s, size_t n, size_t nchunks, size_t per, unsigned chunk_len)
+__device__ __forceinline__ void vec_map_chunk(double *__restrict__ d, const double *__restrict__ a,
+                                              const double *__restrict__ b, double s, size_t n, size_t nchunks,
+                                              size_t per, unsigned chunk_len)
 {
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const size_t i = n - 1;
@@ -113,11 +114,51 @@ __global__ __launch_bounds__(VEC_BLOCK) void vec_map_kernel(double *__restrict__
     }
 }
 
+template <int KIND>
+__global__ __launch_bounds__(VEC_BLOCK) void vec_map_kernel(double *__restrict__ d,
+                                                            const double *__restrict__ a,
+                                                            const double *__restrict__ b,
+                                                            double s, size_t n, size_t nchunks, size_t per, unsigned chunk_len)
+{
+    vec_map_chunk<KIND>(d, a, b, s, n, nchunks, per, chunk_len);
+}
+
+// scale * (*num / *den) of two scalars in HBM: one IEEE division, one multiplication (what a host that had
+// downloaded them would pass on); no den: scale * *num; *den == 0: 0 (a converged solver stays where it is)
+__device__ __forceinline__ double dev_ratio(double scale, const double *num, const double *den)
+{
+    if (!den) return scale * *num;
+    const double q = *den;
+    return q == 0.0 ? 0.0 : scale * (*num / q);
+}
+
+// d = a + c * b with c formed from device scalars, once per workgroup and before its first store
+__global__ __launch_bounds__(VEC_BLOCK) void vec_map_ratio_kernel(double *__restrict__ d,
+                                                                  const double *__restrict__ a,
+                                                                  const double *__restrict__ b, double scale,
+                                                                  const double *num, const double *den, size_t n,
+                                                                  size_t nchunks, size_t per, unsigned chunk_len)
+{
+    vec_map_chunk<2>(d, a, b, dev_ratio(scale, num, den), n, nchunks, per, chunk_len);
+}
+
 __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
     return v;
+}
+
+// a workgroup's sum of `acc` (wavefronts by DPP shuffles, then LDS, in wavefront order); thread 0 has it
+__device__ __forceinline__ double block_sum(double acc, double *wsum)
+{
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < VEC_BLOCK / 64; ++w) t += wsum[w];
+    return t;
 }
 
 // SAME: a vector with itself (a norm): every line is loaded once
@@ -159,29 +200,90 @@ __global__ __launch_bounds__(VEC_BLOCK) void vec_dot_kernel(const double *__rest
             acc = fma(va.y, vb.y, acc);
         }
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < VEC_BLOCK / 64; ++w) t += wsum[w];
-        partials[blockIdx.x] = t;            // (a workgroup without a chunk: 0)
-    }
+    const double t = block_sum(acc, wsum);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;            // (a workgroup without a chunk: 0)
 }
 
 // the workgroups' sums in workgroup order (thread t: t, t + 256, ...; then the wavefronts, then the block)
-__global__ __launch_bounds__(VEC_BLOCK) void vec_dot_final_kernel(double *partials, unsigned nblocks)
+__device__ __forceinline__ double partials_sum(const double *partials, unsigned nblocks, double *wsum)
 {
-    __shared__ double wsum[VEC_BLOCK / 64];
     double acc = 0.0;
     for (unsigned i = threadIdx.x; i < nblocks; i += VEC_BLOCK) acc += partials[i];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    return block_sum(acc, wsum);
+}
+
+// ... to *out: the slot behind the partials (spx_hip_vec_mul copies it to the host) or a client's device scalar
+__global__ __launch_bounds__(VEC_BLOCK) void vec_dot_final_kernel(const double *partials, unsigned nblocks, double *out)
+{
+    __shared__ double wsum[VEC_BLOCK / 64];
+    const double t = partials_sum(partials, nblocks, wsum);
+    if (threadIdx.x == 0) *out = t;
+}
+
+// One CG update in one pass: a = *rr / *pap (0 if *pap == 0); x += a p; r -= a ap; the workgroup's share of the new
+// r . r to partials[blockIdx.x].  One chunk per workgroup as the map kernels (it writes); four operand streams in,
+// two out.  x and r get what vec_map_kernel<2> gives them with the host coefficients a and -a.
+__global__ __launch_bounds__(VEC_BLOCK) void vec_cg_update_kernel(double *__restrict__ x, const double *__restrict__ p,
+                                                                  double *__restrict__ r, const double *__restrict__ ap,
+                                                                  const double *rr, const double *pap,
+                                                                  double *__restrict__ partials, size_t n,
+                                                                  size_t nchunks, size_t per, unsigned chunk_len)
+{
+    __shared__ double wsum[VEC_BLOCK / 64];
+    const double a = dev_ratio(1.0, rr, pap), na = -a;
+    double acc = 0.0;
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const size_t i = n - 1;
+        x[i] = x[i] + a * p[i];
+        const double rn = r[i] + na * ap[i];
+        r[i] = rn;
+        acc = rn * rn;
+    }
+    size_t lo, hi;
+    if (vec_chunk(n / 2, nchunks, per, chunk_len, lo, hi)) {
+        double2 *x2 = reinterpret_cast<double2 *>(x), *r2 = reinterpret_cast<double2 *>(r);
+        const double2 *p2 = reinterpret_cast<const double2 *>(p), *ap2 = reinterpret_cast<const double2 *>(ap);
+        size_t i = lo + threadIdx.x;
+        for (; i + 3 * VEC_BLOCK < hi; i += 4 * VEC_BLOCK) {
+            double2 vx[4], vp[4], vr[4], vq[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                vx[k] = x2[i + k * VEC_BLOCK];
+                vp[k] = p2[i + k * VEC_BLOCK];
+                vr[k] = r2[i + k * VEC_BLOCK];
+                vq[k] = ap2[i + k * VEC_BLOCK];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                x2[i + k * VEC_BLOCK] = vec_map_one<2>(vx[k], vp[k], a);
+                const double2 rn = vec_map_one<2>(vr[k], vq[k], na);
+                r2[i + k * VEC_BLOCK] = rn;
+                acc = fma(rn.x, rn.x, acc);
+                acc = fma(rn.y, rn.y, acc);
+            }
+        }
+        for (; i < hi; i += VEC_BLOCK) {
+            x2[i] = vec_map_one<2>(x2[i], p2[i], a);
+            const double2 rn = vec_map_one<2>(r2[i], ap2[i], na);
+            r2[i] = rn;
+            acc = fma(rn.x, rn.x, acc);
+            acc = fma(rn.y, rn.y, acc);
+        }
+    }
+    const double t = block_sum(acc, wsum);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;            // (a workgroup without a chunk: 0)
+}
+
+// ... and its finish: the new r . r in workgroup order, *beta = new / old (0 if old == 0), *rr = new
+__global__ __launch_bounds__(VEC_BLOCK) void vec_cg_finish_kernel(const double *partials, unsigned nblocks, double *rr,
+                                                                  double *beta)
+{
+    __shared__ double wsum[VEC_BLOCK / 64];
+    const double t = partials_sum(partials, nblocks, wsum);
     if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < VEC_BLOCK / 64; ++w) t += wsum[w];
-        partials[nblocks] = t;
+        const double old = *rr;
+        *beta = old == 0.0 ? 0.0 : t / old;
+        *rr = t;
     }
 }
 
@@ -218,6 +320,36 @@ spx_error_t map(spx_hip_vec_t *d, const spx_hip_vec_t *a, const spx_hip_vec_t *b
                        b ? b->data : nullptr, s, d->size, g.nchunks, g.per, g.chunk);
     VEC_TRY(hipGetLastError());
     return SPX_SUCCESS;
+}
+
+// the dot product's grid: a bounded number of workgroups, several chunks each where the vector is long
+inline VecGrid dot_grid(size_t n)
+{
+    VecGrid g = grid_for(n, VEC_CHUNK_MAX);
+    if (g.blocks > (unsigned) VEC_DOT_BLOCKS) g.blocks = (unsigned) VEC_DOT_BLOCKS & ~7u;
+    return g;
+}
+
+// *out (device memory) <- v1 . v2 through v1->partials: two kernels, nothing else
+spx_error_t enqueue_dot(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, double *out, hipStream_t stream)
+{
+    const VecGrid g = dot_grid(v1->size);
+    if (v1->data == v2->data)
+        hipLaunchKernelGGL(vec_dot_kernel<true>, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, v1->data,
+                           v2->data, v1->partials, v1->size, g.nchunks, g.per, g.chunk);
+    else
+        hipLaunchKernelGGL(vec_dot_kernel<false>, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, v1->data,
+                           v2->data, v1->partials, v1->size, g.nchunks, g.per, g.chunk);
+    hipLaunchKernelGGL(vec_dot_final_kernel, dim3(1), dim3(VEC_BLOCK), 0, stream, v1->partials, g.blocks, out);
+    VEC_TRY(hipGetLastError());
+    return SPX_SUCCESS;
+}
+
+// a device scalar inside the storage of v (NULL: no)
+inline bool inside(const double *s, const spx_hip_vec_t *v)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(s), lo = reinterpret_cast<uintptr_t>(v->data);
+    return s && a >= lo && a < lo + (v->size ? v->size : 1) * sizeof(double);
 }
 
 }  // namespace
@@ -331,19 +463,67 @@ spx_error_t spx_hip_vec_mul(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, sp
     if (same_size(v1, v2) != SPX_SUCCESS) return SPX_FAILURE;
     if (!result) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid result pointer"); return SPX_FAILURE; }
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    VecGrid g = grid_for(v1->size, VEC_CHUNK_MAX);
-    if (g.blocks > (unsigned) VEC_DOT_BLOCKS) g.blocks = (unsigned) VEC_DOT_BLOCKS & ~7u;
-    if (v1->data == v2->data)
-        hipLaunchKernelGGL(vec_dot_kernel<true>, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, v1->data,
-                           v2->data, v1->partials, v1->size, g.nchunks, g.per, g.chunk);
-    else
-        hipLaunchKernelGGL(vec_dot_kernel<false>, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, v1->data,
-                           v2->data, v1->partials, v1->size, g.nchunks, g.per, g.chunk);
-    hipLaunchKernelGGL(vec_dot_final_kernel, dim3(1), dim3(VEC_BLOCK), 0, stream, v1->partials, g.blocks);
-    VEC_TRY(hipGetLastError());
-    VEC_TRY(hipMemcpyAsync(result, v1->partials + g.blocks, sizeof(double),
-                           hipMemcpyDeviceToHost, stream));
+    double *sum = v1->partials + dot_grid(v1->size).blocks;
+    if (enqueue_dot(v1, v2, sum, stream) != SPX_SUCCESS) return SPX_FAILURE;
+    VEC_TRY(hipMemcpyAsync(result, sum, sizeof(double), hipMemcpyDeviceToHost, stream));
     VEC_TRY(hipStreamSynchronize(stream));
+    return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_vec_mul_dev(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, spx_value_t *result_dev,
+                                void *stream)
+{
+    if (same_size(v1, v2) != SPX_SUCCESS) return SPX_FAILURE;
+    if (!result_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid device scalar"); return SPX_FAILURE; }
+    return enqueue_dot(v1, v2, result_dev, static_cast<hipStream_t>(stream));
+}
+
+spx_error_t spx_hip_vec_scale_add_ratio(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, spx_hip_vec_t *v3,
+                                        spx_value_t scale, const spx_value_t *num_dev,
+                                        const spx_value_t *den_dev, void *stream)
+{
+    if (same_size(v1, v2) != SPX_SUCCESS || same_size(v1, v3) != SPX_SUCCESS) return SPX_FAILURE;
+    if (!num_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid device scalar"); return SPX_FAILURE; }
+    if (inside(num_dev, v3) || inside(den_dev, v3)) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "a device scalar lies inside the vector the call writes");
+        return SPX_FAILURE;
+    }
+    if (v3->size == 0) return SPX_SUCCESS;
+    const VecGrid g = grid_for(v3->size, VEC_CHUNK_MAP);
+    hipLaunchKernelGGL(vec_map_ratio_kernel, dim3(g.blocks), dim3(VEC_BLOCK), 0, static_cast<hipStream_t>(stream),
+                       v3->data, v1->data, v2->data, scale, num_dev, den_dev, v3->size, g.nchunks, g.per, g.chunk);
+    VEC_TRY(hipGetLastError());
+    return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_vec_cg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_hip_vec_t *r,
+                                  const spx_hip_vec_t *ap, spx_value_t *rr_dev, const spx_value_t *pap_dev,
+                                  spx_value_t *beta_dev, void *stream_)
+{
+    if (same_size(x, p) != SPX_SUCCESS || same_size(x, r) != SPX_SUCCESS || same_size(x, ap) != SPX_SUCCESS)
+        return SPX_FAILURE;
+    if (!rr_dev || !pap_dev || !beta_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid device scalar"); return SPX_FAILURE; }
+    if (x == p || x == r || x == ap || p == r || p == ap || r == ap) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "x, p, r and ap must be four different vectors");
+        return SPX_FAILURE;
+    }
+    if (rr_dev == pap_dev || rr_dev == beta_dev || pap_dev == beta_dev) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "rr, pap and beta must be three different device scalars");
+        return SPX_FAILURE;
+    }
+    if (inside(rr_dev, x) || inside(pap_dev, x) || inside(beta_dev, x) || inside(rr_dev, r) || inside(pap_dev, r) ||
+        inside(beta_dev, r)) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "a device scalar lies inside a vector the call writes");
+        return SPX_FAILURE;
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // (size 0: the grid of one empty chunk, so that rr and beta are still written)
+    const VecGrid g = grid_for(x->size, VEC_CHUNK_CG);
+    hipLaunchKernelGGL(vec_cg_update_kernel, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, x->data, p->data, r->data,
+                       ap->data, rr_dev, pap_dev, r->partials, x->size, g.nchunks, g.per, g.chunk);
+    hipLaunchKernelGGL(vec_cg_finish_kernel, dim3(1), dim3(VEC_BLOCK), 0, stream, r->partials, g.blocks, rr_dev,
+                       beta_dev);
+    VEC_TRY(hipGetLastError());
     return SPX_SUCCESS;
 }
 
