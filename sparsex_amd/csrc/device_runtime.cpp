@@ -148,6 +148,8 @@ struct DeviceMatrix {
 
 // the multi-vector product (device_spmm): the widest group, and the LDS a workgroup of its kernels may take
 // (two of them fit a CU's 160 KB)
+// (tests/matmat_cases.py holds the budget as MV_LDS_BUDGET_DOUBLES = 10240: its cases are chosen so that their x
+// windows are staged at K = 8, or cannot be -- move the two together)
 constexpr int MV_MAX_GROUP = 8;
 constexpr size_t MV_LDS_BUDGET = (size_t) 80 << 10;
 

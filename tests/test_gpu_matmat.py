@@ -14,24 +14,11 @@ import scipy.sparse as sp
 import sparsex_amd as sx
 from sparsex_amd import synth
 from helpers import GOLDEN, check_y, tune
+from matmat_cases import NOSAMPLE, block as _block, long_rows as _long_rows, run, to_scipy
 
 pytestmark = pytest.mark.gpu
 
 NVECS = (1, 2, 3, 5, 8, 13)
-NOSAMPLE = {"spx.preproc.sampling": "none"}
-
-
-def _long_rows():
-    rng = np.random.RandomState(3)
-    n = 40000
-    rows = np.concatenate([np.full(30000, 5), np.full(9000, 17), rng.randint(0, n, 50000)])
-    cols = np.concatenate([rng.choice(n, 30000, replace=False),
-                           rng.choice(n, 9000, replace=False), rng.randint(0, n, 50000)])
-    a = sp.coo_matrix((np.ones(rows.size), (rows, cols)), shape=(n, n)).tocsr()
-    a.sum_duplicates()
-    a.sort_indices()
-    a.data = rng.uniform(-1, 1, a.nnz)
-    return (a.indptr.astype(np.int32), a.indices.astype(np.int32), a.data, n)
 
 
 def _golden(name):
@@ -78,32 +65,8 @@ def tuned():
     sx.options_reset()
 
 
-def _block(torch, n, nvec, pad, seed0, fill=None):
-    """(nvec, n) float64 view into an (nvec, n + pad) tensor whose padding holds NaN."""
-    full = torch.full((nvec, n + pad), float("nan"), dtype=torch.float64, device="cuda")
-    view = full[:, :n]
-    if fill is None:
-        for j in range(nvec):
-            view[j] = torch.from_numpy(synth.random_x(n, seed=seed0 + j))
-    else:
-        view.fill_(fill)
-    return full, view
-
-
 def _run(torch, A, csr, nvec, alpha, beta, padx=0, pady=0):
-    n = csr[3]
-    xf, X = _block(torch, n, nvec, padx, 11)
-    yf, Y = _block(torch, n, nvec, pady, 101, None if beta != 0.0 else float("nan"))
-    y0 = Y.cpu().numpy().copy()
-    A.matmat(alpha, X, beta, Y)
-    torch.cuda.synchronize()
-    Xh, Yh = X.cpu().numpy(), Y.cpu().numpy()
-    for j in range(nvec):
-        check_y(csr, Xh[j], Yh[j], alpha, beta, y0[j] if beta != 0.0 else None)
-    if pady:
-        assert torch.isnan(yf[:, n:]).all(), "the padding of Y was written"
-    if padx:
-        assert torch.isnan(xf[:, n:]).all()
+    run(torch, A, to_scipy(csr), nvec, alpha, beta, padx, pady)
 
 
 @pytest.mark.parametrize("name", list(CASES))
