@@ -48,7 +48,7 @@ CASES = [
     ("nd24k", lambda: synth.syn_nd24k(0.02), {"spx.preproc.sampling": "none"}),
     ("nd24k-nostack", lambda: synth.syn_nd24k(0.02), {"spx.preproc.sampling": "none", "spx.gpu.stack_segments": "false"}),
     ("webbase", lambda: synth.syn_webbase(0.01), {}),
-    ("webbase-wide", lambda: synth.syn_webbase(0.08), {}),            # u32 column offsets
+    ("webbase-wide", lambda: synth.syn_webbase(0.08), {}),            # 24-bit column offsets (32 bits: limit_cases.py)
     ("webbase-tiny-rb", lambda: synth.syn_webbase(0.01), {"spx.gpu.rowblock_elems": "100", "spx.gpu.rowblock_rows": "11"}),
     ("nlpkkt", lambda: synth.syn_nlpkkt(7), {"spx.preproc.sampling": "none", "spx.rt.nr_threads": "2"}),
     ("all-types", lambda: synth.syn_nlpkkt(6), {"spx.preproc.xform": "all", "spx.preproc.sampling": "none"}),
@@ -86,6 +86,8 @@ def test_general_stream_holds_the_matrix_exactly(tmp_path, name, gen, opts):
     s.check_ownership()
     row0 = s.rbs["row0"].astype(np.int64)[b]
     assert ((r >= row0) & (r < row0 + s.rbs["n_rows"].astype(np.int64)[b])).all()
+    if name == "webbase-wide":
+        assert 3 in set(s.rbs["cidx_width"])
     if name == "web-wide-rows":
         assert int(s.rbs["n_rows"].max()) > 1024
     if name.startswith("band"):
