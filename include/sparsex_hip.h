@@ -151,7 +151,11 @@ extern "C" {
  * graph replayed later reads the new one.
  * Once an exchange plan is attached (spx_hip_mat_dist_attach), the plain entry points above
  * write only the rows this process owns or adds to, [first conflict row, last owned row):
- * the rest of y_dev is left as it is (it is nobody's business any more).
+ * the rest of y_dev is left as it is (it is nobody's business any more).  Inside that range the
+ * owned rows and the conflict rows hold this process' partial vector; a row in front of the owned
+ * ones that the process does not add to is either cleared to 0 or left as it is.
+ * A cut may leave a process a single row (or hand it rows without a nonzero below the diagonal):
+ * such a slice tunes, multiplies and attaches like any other.
  */
 spx_error_t spx_hip_matvec_mult(spx_value_t alpha, const spx_matrix_t *A,
                                 const spx_value_t *x_dev, spx_value_t *y_dev,

@@ -751,9 +751,7 @@ static void emit_and_upload(spx_matrix_t *A)
         // (a matrix that is attached to an exchange plan keeps its limited init range over a
         // re-upload: the state lives with the matrix, not with the device copy)
         if (A->dist && sym) {
-            idx_t first_init = A->first_block_row;
-            if (A->has_tiles && !A->conflict_rows.empty()) first_init = std::min(first_init, A->conflict_rows.front());
-            device_set_init_rows(A->dev, (size_t) first_init);
+            device_set_init_rows(A->dev, (size_t) dist_first_init_row(*A));
         }
         keep_index(A, std::move(gs));
     } else {

@@ -426,12 +426,9 @@ try {
         }
         // the exchange takes over what the caller-side all-reduce needed: rows this
         // process neither owns nor adds to are nobody's business any more
-        // (the thin mirror list stores its rows, it needs no cleared y; spilled tile sums in
-        // front of the row-blocks do)
+        // (from the first conflict row on: dist_first_init_row)
         if (A->dev && A->symmetric) {
-            idx_t first = A->first_block_row;
-            if (A->has_tiles && !A->conflict_rows.empty()) first = std::min(first, A->conflict_rows.front());
-            device_set_init_rows(A->dev, (size_t) first);
+            device_set_init_rows(A->dev, (size_t) dist_first_init_row(*A));
         }
     } catch (const FatalError &e) {
         SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());

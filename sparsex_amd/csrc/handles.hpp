@@ -12,6 +12,7 @@
 #include "xwindows.hpp"
 #include "sxplan.hpp"
 
+#include <algorithm>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -121,3 +122,14 @@ struct matrix {
     std::mutex mtx;
 };
 
+// Symmetric slice with an exchange plan attached: the first row the init pass clears.  The row-blocks in front
+// of the slice start on a row of their own choosing, up to a row-block in front of the first conflict row: the
+// rows before that one receive nothing and, as include/sparsex_hip.h promises, stay as they are.  (The thin
+// mirror list stores its rows and needs no cleared y; spilled tile sums in front of the row-blocks do.)
+inline idx_t dist_first_init_row(const matrix &A)
+{
+    idx_t first = A.first_block_row;
+    if (A.conflict_rows.empty()) return first;
+    if (A.has_tiles) first = std::min(first, A.conflict_rows.front());
+    return std::max(first, std::min(A.conflict_rows.front(), A.own_lo));
+}
