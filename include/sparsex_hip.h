@@ -21,7 +21,9 @@
  *                           nnz/1280 clamped to [1024, 4096]; 8192 beyond 64 M)
  *   spx.gpu.waves           wavefronts per workgroup of the SpMV kernel: 2, 4 or 8;
  *                           0 (default): spx_mat_tune() measures a few launch
- *                           configurations on the device and keeps the fastest
+ *                           configurations on the device and keeps the fastest.  (The multi-vector kernel of
+ *                           spx.gpu.sym_matmat runs eight where its LDS leaves a compute unit room for fewer than
+ *                           four workgroups, whatever is set or measured here.)
  *   spx.gpu.rowblock_rows   max rows per row-block (default 512; up to 2048: planned row-blocks of
  *                           at most 512 rows are then joined up to the target size -- for matrices
  *                           with a few nonzeros per row; measured on syn-webbase: 38.8 us with 512,
@@ -68,6 +70,14 @@
  *                           tile and common slots, so that a column several of them reach is
  *                           handed to y once (default 1024, at most 2048; measured on syn-nlpkkt,
  *                           734 M nonzeros: 512 0.842 ms, 1024 0.826 ms, 2048 0.92 ms)
+ *   spx.gpu.sym_matmat      symmetric path with tiles or read-once segments: "false" (default) | "true" -- the
+ *                           read-once passes serve groups of vectors (spx_hip_matmat_kernel reads the stored triangle
+ *                           once per group, csx_spmv_mvsym_kernel).  Read where the device copy is built (spx_mat_tune,
+ *                           spx_mat_restore; not part of a saved matrix).  At tune time it makes spx.gpu.sym_spill=auto
+ *                           "atomic" without a measurement and spx.gpu.sym_wide_rows at most 512, so that K copies of a
+ *                           row-block's slots and y tile fit the LDS; an explicit "lists", spx.gpu.deterministic=true or
+ *                           spx.gpu.wave_tiles=true keep their meaning and the group stays 1.  General matrices and
+ *                           spx.gpu.sym_once=false ignore it; any other value fails spx_mat_tune
  *   spx.gpu.sym_pipeline    symmetric path, streams of read-once segments: "auto" (default: measured at tune time) |
  *                           "true" | "false" -- passes whose lanes all belong to one unit carry their geometry in a
  *                           device-side copy of their header, so that values and x are requested in one round trip
@@ -176,14 +186,19 @@ spx_error_t spx_hip_matvec_kernel(spx_value_t alpha, const spx_matrix_t *A,
  * with nvec > 0, ldx < ncols, ldy < nrows, overlapping X and Y, a host-only matrix or the wrong current device.
  * One pass over the matrix' stream serves spx_hip_matmat_group(A) vectors (the values, descriptors and column
  * offsets are read once for all of them); streams with symmetric tiles or read-once segments (the default
- * symmetric tune) run one single-vector product per column -- exact, no faster: tune a symmetric matrix with
- * spx.gpu.sym_once=false, or as a general one, for the multi-vector kernels.  Nothing is allocated.
+ * symmetric tune) run one single-vector product per column -- exact, no faster -- unless they were tuned or
+ * restored with spx.gpu.sym_matmat=true: then a pass over the stored triangle serves a group of 8, 4 or 2 vectors
+ * wherever the transposed sums are handed over with global atomics and one tile per workgroup is kept (not with
+ * spx.gpu.sym_spill=lists, spx.gpu.deterministic=true or spx.gpu.wave_tiles=true).  Such columns go through
+ * atomics: within the fp64 bound of the product, not bit-reproducible.  Nothing is allocated.
  */
 spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                   const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                   spx_value_t *Y_dev, size_t ldy, void *stream);
 /* Diagnostic: how many vectors one pass over this matrix' stream serves (>= 2: the multi-vector
- * kernels run; 1: one product per vector), -1 for a matrix without a device copy. */
+ * kernels run; 1: one product per vector), -1 for a matrix without a device copy.  A symmetric tune with tiles or
+ * read-once segments: 1, or under spx.gpu.sym_matmat=true the widest of 8, 4, 2 of which that many copies of the
+ * largest row-block's slots and y tile fit 80 KB of LDS (two workgroups per compute unit). */
 int spx_hip_matmat_group(const spx_matrix_t *A);
 
 /* ---- device-resident vectors ---------------------------------------------------

@@ -725,6 +725,7 @@ static void emit_and_upload(spx_matrix_t *A)
     gs.xw_on = A->xw_on;
     gs.sx_plan = sym && A->sym_pipeline != 0 && !A->deterministic && A->wave_tiles != 1;
     gs.sx_on = A->sx_on;
+    gs.sym_matmat = A->sym_matmat;
     gs.sym_atomic = A->sym_atomic && !A->deterministic;
     gs.deterministic = A->deterministic;
     gs.wave_tiles = A->deterministic || A->wave_tiles == 1;
@@ -1134,6 +1135,22 @@ static spx_matrix_t *do_tune(spx_input_t *in)
     A->deterministic = cfg.get_bool("spx.gpu.deterministic");
     A->sym_atomic = spill_mode == "atomic" && !A->deterministic;
     A->spill_mode = spill_mode == "lists" ? 0 : (spill_mode == "atomic" ? 1 : -1);
+    {
+        // spx.gpu.sym_matmat: the read-once passes of a symmetric stream serve groups of vectors
+        // (csx_spmv_mvsym_kernel).  That kernel hands over with global atomics only and keeps K copies of a
+        // row-block's slots and y tile in LDS: the hand-over is atomic where it would have been measured, and no
+        // wide row-blocks are emitted.  General matrices and tunes without read-once passes ignore it.
+        const std::string sm = cfg.get_str("spx.gpu.sym_matmat");
+        if (sm != "true" && sm != "false") {
+            log_msg(LOG_ERR, "spx.gpu.sym_matmat: true or false\n");
+            throw FatalError("bad spx.gpu.sym_matmat");
+        }
+        A->sym_matmat = sm == "true" && sym && A->emit_params.sym_once;
+        if (A->sym_matmat) {
+            if (spill_mode == "auto" && !A->deterministic) A->sym_atomic = true;
+            A->emit_params.wide_rows = std::min<size_t>(A->emit_params.wide_rows, SPX_MAX_RB_ROWS);
+        }
+    }
     const std::string wt_mode = cfg.get_str("spx.gpu.wave_tiles");
     if (wt_mode != "auto" && wt_mode != "true" && wt_mode != "false") {
         log_msg(LOG_ERR, "spx.gpu.wave_tiles: true, false or auto\n");
@@ -1180,7 +1197,7 @@ static spx_matrix_t *do_tune(spx_input_t *in)
         A->col_phases = 1;                              // (over-long rows: no phases)
         emit_and_upload(A.get());
     }
-    const bool tune_spill = spill_mode == "auto" && !A->deterministic && !A->has_symsegs;
+    const bool tune_spill = spill_mode == "auto" && !A->deterministic && !A->has_symsegs && !A->sym_matmat;
     const bool tune_wt = wt_mode == "auto" && !A->deterministic && !A->has_symsegs;
     const bool tune_xw = xw_mode == "auto" && !A->deterministic && !sym;
     const double t_auto = now_sec();
@@ -1870,6 +1887,8 @@ try {
     A->host_only = cfg.get_bool("spx.rt.host_only");
     A->device_ordinal = (int) cfg.get_long("spx.rt.device");
     A->full_colind = cfg.get_bool("spx.matrix.full_colind");
+    // (not part of the file: a restored matrix serves the group that the option NOW and its stream allow)
+    A->sym_matmat = gs->sym_matmat = A->symmetric && cfg.get_str("spx.gpu.sym_matmat") == "true";
     if (A->symmetric && !gs->sym_fused) stream_touched_rows(*gs, A->own_lo, A->conflict_rows);
     if (A->own_lo > 0 || A->own_hi < A->nrows) stream_read_cols(*gs, A->own_lo, A->own_hi, (size_t) A->ncols, A->halo_cols);
     A->first_block_row = A->own_lo;

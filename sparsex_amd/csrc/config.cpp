@@ -67,6 +67,7 @@ void Config::reset_defaults()
     props_["spx.gpu.sym_segment_max"] = "8";   // ... and the widest segment a longer run is cut into (4: every segment can ride the read-once pipeline)
     props_["spx.gpu.sym_wide_rows"] = "1024";  // rows of a row-block with read-once segments (several planned row-blocks side by side)
     props_["spx.gpu.sym_spill"] = "auto";      // symmetric tiles' transposed sums: lists | atomic | auto (measured)
+    props_["spx.gpu.sym_matmat"] = "false";    // symmetric, read-once passes: groups of vectors per pass over the stream (spx_hip_matmat_kernel): true | false
     props_["spx.gpu.sym_remine"] = "true";     // symmetric: re-cut the mirrored triangle into row segments
     props_["spx.gpu.sym_pure_passes"] = "true"; // symmetric, read-once segments: long runs fill passes of their own (one descriptor, in the header)
     props_["spx.gpu.sym_pipeline"] = "auto";   // ... and those passes run pipelined, x requested with the values (csx_spmv_sx_kernel): true | false | auto (measured)

@@ -38,6 +38,10 @@ struct DeviceMatrix {
     // MV_MAX_GROUP vectors, the most rows and the longest x window of a row-block
     double *carry_mv = nullptr;
     uint32_t mv_rows = 0, mv_xwin = 0;
+    // ... on a symmetric stream with read-once passes (spx.gpu.sym_matmat, csx_spmv_mvsym_kernel): the option, the
+    // most slots + rows of a row-block, and the most slots + rows + x window
+    bool sym_matmat = false;
+    uint32_t mvsym_core = 0, mvsym_full = 0;
     SpxRowBlock *rbs = nullptr;
     double *values = nullptr;
     SpxUnitDesc *descs = nullptr;
@@ -152,6 +156,14 @@ struct DeviceMatrix {
 // windows are staged at K = 8, or cannot be -- move the two together)
 constexpr int MV_MAX_GROUP = 8;
 constexpr size_t MV_LDS_BUDGET = (size_t) 80 << 10;
+// ... of csx_spmv_mvsym_kernel (symmetric streams with read-once passes, spx.gpu.sym_matmat): K copies of
+// {slots, y tile}, and the K x windows where they fit as well.  Two workgroups per CU, K = 2 on a row-block of 512 rows and all its slots: measured
+// against a CU's whole 160 KB (one workgroup, K = 4 there) on syn-nlpkkt e240, 942 against 997 us per vector; syn-nd24k
+// runs K = 8 in 32 KB either way (profiles/r10/MATMAT_SYM.md).  A workgroup that leaves room for fewer than four of
+// its kind (more than MVSYM_LDS_FEW) runs eight wavefronts whatever the single-vector product runs with: the
+// wavefronts of a CU are all that hides a pass' dependent loads.
+constexpr size_t MVSYM_LDS_BUDGET = (size_t) 80 << 10;
+constexpr size_t MVSYM_LDS_FEW = (size_t) 40 << 10;
 
 // the host-vector entry point (device_spmv_host)
 constexpr size_t STAGE_PIECE = (size_t) 16 << 20;      // bytes
@@ -285,6 +297,17 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
         }
         place.put(&m->carry_mv, no_doubles, (size_t) MV_MAX_GROUP * (s.n_carry ? s.n_carry : 1));
         spmv_mv_allow_lds(160u * 1024u);
+    } else if (symmetric && s.sym_matmat) {
+        // (read-once passes for K vectors: device_mv_group decides from what the stream and its settings allow)
+        m->sym_matmat = true;
+        for (const SpxRowBlock &rb : s.rbs) {
+            m->mv_xwin = std::max<uint32_t>(m->mv_xwin, rb.xwin_len);
+            m->mvsym_core = std::max<uint32_t>(m->mvsym_core, (uint32_t) rb.n_slots + rb.n_rows);
+            m->mvsym_full = std::max<uint32_t>(m->mvsym_full, (uint32_t) rb.n_slots + rb.n_rows + rb.xwin_len);
+        }
+        place.put(&m->carry_mv, no_doubles, (size_t) MV_MAX_GROUP * (s.n_carry ? s.n_carry : 1));
+        spmv_mv_allow_lds(160u * 1024u);
+        spmv_mvsym_allow_lds(160u * 1024u);
     }
     for (const SpxRowBlock &rb : s.rbs)
         for (uint32_t k = 0; k < rb.n_pass && !m->has_symsegs; ++k)
@@ -695,10 +718,31 @@ static size_t mv_lds_bytes(const DeviceMatrix *m, int K, bool stage)
     return ((size_t) K * (mv_copies(m) * m->mv_rows + (stage ? m->mv_xwin : 0u))) * sizeof(double);
 }
 
+// LDS of a workgroup of csx_spmv_mvsym_kernel: K x {slots, y tile}, with (stage) or without the K x windows,
+// and the slot groups' columns
+static size_t mvsym_lds_bytes(const DeviceMatrix *m, int K, bool stage)
+{
+    return (size_t) K * (stage ? m->mvsym_full : m->mvsym_core) * sizeof(double) + m->max_slot_groups * sizeof(uint32_t);
+}
+
+// symmetric streams with read-once passes serve a group where spx.gpu.sym_matmat asked for it and everything is
+// handed over with global atomics by one tile per workgroup
+static bool mvsym_on(const DeviceMatrix *m)
+{
+    return m->has_tiles && m->sym_matmat && m->sym_atomic && !m->wave_tiles && m->carry_mv;
+}
+
 // the widest group whose y tiles fit MV_LDS_BUDGET (from the tune-time settings: row-blocks, waves, tiles per
 // wavefront); 1 where only the single-vector product runs
 int device_mv_group(const DeviceMatrix *m)
 {
+    if (mvsym_on(m)) {
+        // (K x {slots, y tile} of the largest row-block and the slot groups' columns; the x windows are the launch's
+        // business: staged where they fit as well, launch_rowblocks_mv)
+        for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
+            if (mvsym_lds_bytes(m, K, false) <= MVSYM_LDS_BUDGET) return K;
+        return 1;
+    }
     if (m->has_tiles || !m->carry_mv) return 1;
     for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
         if (mv_lds_bytes(m, K, false) <= MV_LDS_BUDGET) return K;
@@ -717,6 +761,16 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
     mv.x = a.x; mv.y = a.y; mv.ldx = ldx; mv.ldy = ldy;
     mv.carry = m->carry_mv; mv.n_carry = mv_n_carry(m);
     mv.dvalues = a.dvalues; mv.alpha = a.alpha; mv.beta = a.beta; mv.pass_stride = a.pass_stride;
+    if (m->has_tiles) {
+        // read-once passes (device_mv_group: mvsym_on): the K x windows behind the K x {slots, y tile} where they fit
+        MvSymArgs ms{};
+        static_cast<MvArgs &>(ms) = mv;
+        ms.slot_col = a.slot_col;
+        ms.stage = m->mv_xwin && mvsym_lds_bytes(m, K, true) <= MVSYM_LDS_BUDGET ? 1u : 0u;
+        const size_t lds = mvsym_lds_bytes(m, K, ms.stage != 0);
+        launch_spmv_mvsym(K, lds > MVSYM_LDS_FEW ? MAX_WAVES_PER_BLOCK : m->waves, blocks, lds, stream, ms, xcd_now);
+        return;
+    }
     // the K x windows in LDS where they fit next to the tiles; else SPX_PASS_GATHER_LDS gathers through L2
     mv.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
     const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
@@ -726,7 +780,7 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
 // Y <- alpha*A*X + beta*Y for K vectors (column-major: vector j of X at X + j * ldx, of Y at Y + j * ldy) in one
 // sequence of launches: init or scale, the row-blocks of every column phase, fix-up.  K == 1 runs the kernel that
 // the stream and the matrix' settings call for (launch_rowblocks), K = 2, 4, 8 (device_mv_group: streams without
-// symmetric tiles or read-once segments) the K-vector kernels over the plain stream.
+// symmetric tiles or read-once segments, or with spx.gpu.sym_matmat) the K-vector kernels over the plain stream.
 static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
                            size_t ldy, void *stream_, const SpmvPart *part)
 {
@@ -801,8 +855,8 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
 }
 
 // Y <- alpha*A*X + beta*Y for nvec column-major vectors: groups of K vectors served by one pass over the plain
-// stream.  Streams with symmetric tiles or read-once segments, and a last vector on its own, run the
-// single-vector product: exact, column by column.
+// stream.  Streams with symmetric tiles or read-once segments (but under spx.gpu.sym_matmat), and a last vector on
+// its own, run the single-vector product: exact, column by column.
 void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
                  size_t ldy, void *stream_)
 {

@@ -85,6 +85,9 @@ struct GpuStream {
     // spx.gpu.sym_pipeline (device side only, sxplan.hpp): plan the read-once pipeline at upload, and whether
     // the product starts out using it (the launch tuner measures both)
     bool sx_plan = false, sx_on = false;
+    // spx.gpu.sym_matmat (device side only, not saved): a symmetric stream with read-once passes serves groups of
+    // vectors where its hand-over and its LDS allow (device_mv_group)
+    bool sym_matmat = false;
     // accounting
     size_t nnz_stored = 0;        // nonzeros held in `values` (without padding)
     size_t n_unit_elems = 0;

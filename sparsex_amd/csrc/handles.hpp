@@ -102,6 +102,7 @@ struct matrix {
     bool has_symtiles = false;  // the stream holds dense 8x8 tiles (SPX_PASS_SYMTILE)
     bool has_symsegs = false;   // the stream holds read-once row segments (SPX_PASS_SYMSEG): atomic hand-over only
     int spill_mode = -1;        // spx.gpu.sym_spill as asked for: 0 lists, 1 atomic, -1 auto
+    bool sym_matmat = false;    // spx.gpu.sym_matmat on a symmetric tune with read-once passes
     int wave_tiles = -1;        // per-wavefront y tiles: 1 / 0, -1 = measured at tune time (spx.gpu.wave_tiles)
     int unit_windows = -1;      // spx.gpu.unit_windows: 1 / 0, -1 = measured at tune time
     bool xw_on = false;         // ... the product runs with the unit windows of x in LDS (csx_spmv_xw_kernel)

@@ -1,6 +1,7 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the four interpreter translation
-// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_mv_kernels.hip).  Plain C++: no
+// XCD-aware row-block order, the kernel families and the launchers of the five interpreter translation
+// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_mv_kernels.hip,
+// spmv_mvsym_kernels.hip).  Plain C++: no
 // HIP header, so that the host runtime (device_runtime.cpp) is compiled by the host compiler.
 #pragma once
 
@@ -114,5 +115,15 @@ enum class MvFamily {
 void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
                     const XcdSplit &xs);
 void spmv_mv_allow_lds(size_t bytes);
+
+// spmv_mvsym_kernels.hip: the multi-vector product on symmetric streams with read-once passes
+// (SPX_PASS_SYMTILE, SPX_PASS_SYMSEG; spx.gpu.sym_matmat), atomic hand-over, over the plain pass table.
+// (slot_col behind the fields of MvArgs: their order decides how they arrive in SGPRs, see StreamArgs)
+struct MvSymArgs : MvArgs {
+    const uint32_t *slot_col;  // the first column of every group of eight transposed-sum slots
+};
+void launch_spmv_mvsym(int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvSymArgs &a,
+                       const XcdSplit &xs);
+void spmv_mvsym_allow_lds(size_t bytes);
 
 }  // namespace spx

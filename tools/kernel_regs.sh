@@ -2,13 +2,13 @@
 # Registers, scratch and LDS of every kernel of the interpreter's translation units (cross-compiled, no GPU
 # needed):
 #   tools/kernel_regs.sh [pattern] [extra hipcc flags]
-# SPX_TU: the units, default all four ("spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_mv_kernels"; any
-# other .hip file of sparsex_amd/csrc works too).  They compile side by side and leave their assembly in
+# SPX_TU: the units, default all five ("spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_mv_kernels
+# spmv_mvsym_kernels"; any other .hip file of sparsex_amd/csrc works too).  They compile side by side and leave their assembly in
 # /tmp/spx_asm/<unit>.s
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p /tmp/spx_asm
-units=${SPX_TU:-spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_mv_kernels}
+units=${SPX_TU:-spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_mv_kernels spmv_mvsym_kernels}
 for tu in $units; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -munsafe-fp-atomics -Iinclude -Isparsex_amd/csrc \
         ${2:-} -S --cuda-device-only -o /tmp/spx_asm/$tu.s sparsex_amd/csrc/$tu.hip 2>/dev/null &

@@ -6,7 +6,10 @@ For every config and k = 1, 2, 4, 8: one spx_hip_matmat_kernel over a (k, n) blo
 spx_hip_matvec_kernel calls on the same columns; every column of the block product is gated on the single
 products (relative 1e-6, the reference's criterion).  One JSON line per config:
 
-    python3 tools/matmat_bench.py [--configs cant,nd24k,webbase,e240,nd24k-sym,e240-sym] [--edge 240]
+    python3 tools/matmat_bench.py [--configs cant,nd24k,webbase,e240,nd24k-sym,e240-sym,nd24k-sym-mv,e240-sym-mv] [--edge 240]
+
+The configs of one run share a process, so their times compare (A/B inside one process: separate processes differ
+by up to 15 % on syn-nlpkkt).
 """
 import argparse
 import json
@@ -31,6 +34,9 @@ CONFIGS = {
     "e240": ("syn-nlpkkt", False, {}),
     "nd24k-sym": ("syn-nd24k", True, {}),
     "e240-sym": ("syn-nlpkkt", True, {}),
+    # the symmetric tune with spx.gpu.sym_matmat: its read-once passes serve groups of vectors
+    "nd24k-sym-mv": ("syn-nd24k", True, {"spx.gpu.sym_matmat": "true"}),
+    "e240-sym-mv": ("syn-nlpkkt", True, {"spx.gpu.sym_matmat": "true"}),
 }
 
 
