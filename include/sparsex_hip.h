@@ -102,6 +102,10 @@
  *                           as a software pipeline (csx_spmv_xw_kernel); spx.gpu.unit_window_doubles (3072): most
  *                           doubles of x a row-block may stage (row-blocks that need more gather through L2);
  *                           spx.gpu.unit_window_gap (16): column intervals closer than this are staged as one
+ *   spx.gpu.trans_windows   transposed product of a general matrix (spx_hip_matvec_trans_kernel): "auto" (default: where
+ *                           the window plan stages fewer doubles than it serves nonzeros) | "true" | "false" -- unit passes
+ *                           accumulate in the row-block's unit windows in LDS, which are added to y once, instead of one
+ *                           atomic add per nonzero; read by spx_mat_tune / spx_mat_restore, not saved with the matrix
  *   spx.vec.device          "false" (default) | "true" (also: env SPX_VEC_DEVICE through spx_options_set_from_env):
  *                           vectors the library allocates itself (spx_vec_create, spx_vec_create_random; page-locked)
  *                           keep x's HBM copy between spx_matvec_* calls, reused while no spx_vec_* call has changed
@@ -173,6 +177,32 @@ spx_error_t spx_hip_matvec_mult(spx_value_t alpha, const spx_matrix_t *A,
 spx_error_t spx_hip_matvec_kernel(spx_value_t alpha, const spx_matrix_t *A,
                                   const spx_value_t *x_dev, spx_value_t beta,
                                   spx_value_t *y_dev, void *stream);
+
+/* ---- transposed product -------------------------------------------------------------
+ * y <- alpha*A^T*x + beta*y on device memory, over the stream A was tuned into: no second tune, no second copy
+ * of the matrix.  x_dev: nrows doubles, y_dev: ncols doubles, HBM pointers on the matrix's device; enqueues
+ * only (hipGraph-capturable), allocates nothing.  _mult is _kernel with beta = 0; beta == 0 never reads y_dev.
+ * A symmetric matrix (any tune, slice or attached) runs spx_hip_matvec_kernel: the same result, the same rows.
+ * A general matrix adds every product a(r,c)*x[r] to y[c] with atomics -- in LDS first where its unit windows
+ * allow (spx.gpu.trans_windows = true | false | auto, read by spx_mat_tune / spx_mat_restore, not saved), then
+ * in memory: the result lies within the fp64 bound of the product but is NOT bit-reproducible, and
+ * spx.gpu.deterministic does not cover this call.  A general row slice (spx.rt.gpu_world > 1) reads only its own
+ * rows of the full-length x_dev (global row numbers) and leaves this process' partial vector over ALL columns in
+ * y_dev, to be summed over processes by the caller.
+ * SPX_FAILURE (through the error handler) for a NULL handle or pointer, overlapping x and y ranges, a host-only
+ * matrix, the wrong current device, a general matrix with an exchange plan attached, and (_vec) vectors whose
+ * sizes are not nrows / ncols.
+ */
+spx_error_t spx_hip_matvec_trans_mult(spx_value_t alpha, const spx_matrix_t *A,
+                                      const spx_value_t *x_dev, spx_value_t *y_dev,
+                                      void *stream);
+spx_error_t spx_hip_matvec_trans_kernel(spx_value_t alpha, const spx_matrix_t *A,
+                                        const spx_value_t *x_dev, spx_value_t beta,
+                                        spx_value_t *y_dev, void *stream);
+/* Diagnostic: how the transposed product of this matrix runs.  -1: no device copy (or a NULL handle);
+ * 0: symmetric, the forward product runs; 1: one atomic add per nonzero; 2: unit windows accumulate in LDS and
+ * go to y once each (row-blocks and passes without windows still add per nonzero). */
+int spx_hip_matvec_trans_mode(const spx_matrix_t *A);
 
 /* ---- multi-vector product ----------------------------------------------------------
  * Y <- alpha*A*X + beta*Y for nvec vectors at once, on device memory.
@@ -275,6 +305,10 @@ spx_error_t spx_hip_probe_read_write(const spx_hip_vec_t *src, spx_hip_vec_t *ds
 spx_error_t spx_hip_matvec_kernel_vec(spx_value_t alpha, const spx_matrix_t *A,
                                       const spx_hip_vec_t *x, spx_value_t beta,
                                       spx_hip_vec_t *y, void *stream);
+/* y <- alpha*A^T*x + beta*y on device vectors (x: nrows, y: ncols elements); see spx_hip_matvec_trans_kernel */
+spx_error_t spx_hip_matvec_trans_kernel_vec(spx_value_t alpha, const spx_matrix_t *A,
+                                            const spx_hip_vec_t *x, spx_value_t beta,
+                                            spx_hip_vec_t *y, void *stream);
 
 /* ---- one process per GPU: row-partitioned matrices -------------------------------
  * The reference partitions the rows over the threads of one process

@@ -153,6 +153,11 @@ def lib():
     L.spx_hip_vec_scale_add_ratio.argtypes = [vp, vp, vp, d, vp, vp, vp]
     L.spx_hip_vec_cg_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.spx_hip_matvec_kernel_vec.argtypes = [d, vp, vp, d, vp, vp]
+    L.spx_hip_matvec_trans_mult.argtypes = [d, vp, vp, vp, vp]
+    L.spx_hip_matvec_trans_kernel.argtypes = [d, vp, vp, d, vp, vp]
+    L.spx_hip_matvec_trans_kernel_vec.argtypes = [d, vp, vp, d, vp, vp]
+    L.spx_hip_matvec_trans_mode.restype = C.c_int
+    L.spx_hip_matvec_trans_mode.argtypes = [vp]
     L.spx_log_disable_all.restype = None
     L.spx_log_error_console.restype = None
     _lib = L
@@ -266,6 +271,44 @@ class Matrix:
         rc = lib().spx_hip_matvec_kernel(alpha, self.handle, x_ptr, beta, y_ptr, stream)
         if rc != SPX_SUCCESS:
             raise SpxError("spx_hip_matvec_kernel failed (see stderr)")
+
+    def hip_matvec_trans_kernel(self, alpha, x_ptr, beta, y_ptr, stream=0):
+        """``spx_hip_matvec_trans_kernel``: y <- alpha*A^T*x + beta*y on HBM pointers (x: nrows doubles,
+        y: ncols doubles)."""
+        rc = lib().spx_hip_matvec_trans_kernel(alpha, self.handle, x_ptr, beta, y_ptr, stream)
+        if rc != SPX_SUCCESS:
+            raise SpxError("spx_hip_matvec_trans_kernel failed (see stderr)")
+
+    def trans_mode(self):
+        """``spx_hip_matvec_trans_mode``: -1 no device copy, 0 symmetric (the forward product runs), 1 one
+        atomic add per nonzero, 2 unit windows accumulate in LDS."""
+        return int(lib().spx_hip_matvec_trans_mode(self.handle))
+
+    def matvec_trans(self, alpha, x, beta, y, stream=None):
+        """y <- alpha*A^T*x + beta*y for 1-D contiguous torch float64 tensors on the matrix' device: x of nrows
+        elements, y of ncols.  `stream`: a torch stream (default: the current one of y's device).  Returns y."""
+        import torch
+        pairs = (("x", x, self.nrows), ("y", y, self.ncols))
+        for name, t, n in pairs:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a torch tensor" % name)
+            if t.dtype != torch.float64:
+                raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+            if t.dim() != 1 or t.shape[0] != n:
+                raise ValueError("%s must have the shape (%d,), not %s" % (name, n, tuple(t.shape)))
+            if t.shape[0] > 1 and t.stride(0) != 1:
+                raise ValueError("%s needs stride(0) == 1, not %d" % (name, t.stride(0)))
+        for name, t, n in pairs:
+            if t.device.type != "cuda":
+                raise ValueError("%s must live on the matrix' HIP device, not on %s" % (name, t.device))
+        if x.device != y.device:
+            raise ValueError("x and y live on different devices (%s, %s)" % (x.device, y.device))
+        inf = self.info()
+        if inf.on_device and x.device.index != inf.device:
+            raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, x.device))
+        st = stream if stream is not None else torch.cuda.current_stream(y.device)
+        self.hip_matvec_trans_kernel(alpha, x.data_ptr(), beta, y.data_ptr(), st.cuda_stream)
+        return y
 
     def hip_matmat_kernel(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
         """``spx_hip_matmat_kernel``: Y <- alpha*A*X + beta*Y for nvec column-major vectors in HBM
@@ -573,6 +616,13 @@ def matvec_kernel_vec(A, alpha, x, beta, y, stream=0):
     rc = lib().spx_hip_matvec_kernel_vec(alpha, A.handle, x.handle, beta, y.handle, stream)
     if rc != SPX_SUCCESS:
         raise SpxError("spx_hip_matvec_kernel_vec failed (see stderr)")
+
+
+def matvec_trans_kernel_vec(A, alpha, x, beta, y, stream=0):
+    """``spx_hip_matvec_trans_kernel_vec``: y <- alpha*A^T*x + beta*y on DeviceVectors (x: nrows, y: ncols)."""
+    rc = lib().spx_hip_matvec_trans_kernel_vec(alpha, A.handle, x.handle, beta, y.handle, stream)
+    if rc != SPX_SUCCESS:
+        raise SpxError("spx_hip_matvec_trans_kernel_vec failed (see stderr)")
 
 
 def cg_update(x, p, r, ap, scalars, stream=0):

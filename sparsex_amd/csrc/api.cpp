@@ -747,6 +747,7 @@ static void emit_and_upload(spx_matrix_t *A)
     if (!A->host_only) {
         A->dev = device_upload(gs, (size_t) A->nrows, (size_t) A->ncols, sym, A->own_lo, A->own_hi,
                                A->device_ordinal);
+        device_set_trans_windows(A->dev, A->trans_windows);
         log_msg(LOG_INFO, "descriptor stream: emitted in %.2f s, finalized in %.2f s, uploaded in %.2f s (%zu row-blocks)\n",
                 t_emit1 - t_emit0, t_emit2 - t_emit1, now_sec() - t_emit2, gs.rbs.size());
         // (a matrix that is attached to an exchange plan keeps its limited init range over a
@@ -949,6 +950,18 @@ static void autotune_launch(spx_matrix_t *A, bool tune_waves, bool tune_spill, b
     device_set_xw(A->dev, best_xw);
     log_msg(LOG_INFO, "launch autotune: %d wavefronts per workgroup, row-block scale %.2f%s, unit windows %s (%.2f us per SpMV)\n",
             best_waves, best_scale, A->rb_joined ? ", joined" : "", best_xw ? "on" : "off", 1e6 * best_t);
+}
+
+// spx.gpu.trans_windows: how the transposed product of a general matrix adds (device_set_trans_windows).  Read
+// where the device copy is built, never at product time; not saved with the matrix.
+static int read_trans_windows()
+{
+    const std::string tw = Config::instance().get_str("spx.gpu.trans_windows");
+    if (tw != "auto" && tw != "true" && tw != "false") {
+        log_msg(LOG_ERR, "spx.gpu.trans_windows: true, false or auto\n");
+        throw FatalError("bad spx.gpu.trans_windows");
+    }
+    return tw == "auto" ? -1 : (tw == "true" ? 1 : 0);
 }
 
 static spx_matrix_t *do_tune(spx_input_t *in)
@@ -1173,6 +1186,7 @@ static spx_matrix_t *do_tune(spx_input_t *in)
     }
     A->unit_windows = xw_mode == "auto" ? -1 : (xw_mode == "true" ? 1 : 0);
     A->xw_on = xw_mode == "true";                       // (auto: off until measured)
+    A->trans_windows = read_trans_windows();
     const std::string sx_mode = cfg.get_str("spx.gpu.sym_pipeline");
     if (sx_mode != "auto" && sx_mode != "true" && sx_mode != "false") {
         log_msg(LOG_ERR, "spx.gpu.sym_pipeline: true, false or auto\n");
@@ -1889,6 +1903,12 @@ try {
     A->full_colind = cfg.get_bool("spx.matrix.full_colind");
     // (not part of the file: a restored matrix serves the group that the option NOW and its stream allow)
     A->sym_matmat = gs->sym_matmat = A->symmetric && cfg.get_str("spx.gpu.sym_matmat") == "true";
+    try {
+        A->trans_windows = read_trans_windows();
+    } catch (const FatalError &) {
+        SETERROR_0(SPX_ERR_TUNED_MAT);
+        return SPX_INVALID_MAT;
+    }
     if (A->symmetric && !gs->sym_fused) stream_touched_rows(*gs, A->own_lo, A->conflict_rows);
     if (A->own_lo > 0 || A->own_hi < A->nrows) stream_read_cols(*gs, A->own_lo, A->own_hi, (size_t) A->ncols, A->halo_cols);
     A->first_block_row = A->own_lo;
@@ -1897,6 +1917,7 @@ try {
         if (!A->host_only) {
             A->dev = device_upload(*gs, (size_t) A->nrows, (size_t) A->ncols, A->symmetric != 0,
                                    A->own_lo, A->own_hi, A->device_ordinal);
+            device_set_trans_windows(A->dev, A->trans_windows);
             keep_index(A.get(), std::move(*gs));
         } else {
             A->host_stream = std::move(gs);
@@ -2184,6 +2205,42 @@ try {
     }
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_matvec_trans_mult(spx_value_t alpha, const spx_matrix_t *A,
+                                      const spx_value_t *x_dev, spx_value_t *y_dev, void *stream)
+try {
+    return spx_hip_matvec_trans_kernel(alpha, A, x_dev, 0.0, y_dev, stream);
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_matvec_trans_kernel(spx_value_t alpha, const spx_matrix_t *A,
+                                        const spx_value_t *x_dev, spx_value_t beta,
+                                        spx_value_t *y_dev, void *stream)
+try {
+    if (check_dev(A, x_dev, y_dev) != SPX_SUCCESS) return SPX_FAILURE;
+    // x: the rows, y: the columns; the two ranges must not meet
+    const uintptr_t x0 = (uintptr_t) x_dev, x1 = x0 + (size_t) A->nrows * sizeof(double);
+    const uintptr_t y0 = (uintptr_t) y_dev, y1 = y0 + (size_t) A->ncols * sizeof(double);
+    if (x0 < y1 && y0 < x1) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "vectors x and y overlap");
+        return SPX_FAILURE;
+    }
+    if (A->dist && !A->symmetric) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "no transposed product on a general matrix with an exchange plan attached");
+        return SPX_FAILURE;
+    }
+    try {
+        device_spmv_trans(A->dev, alpha, x_dev, beta, y_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+int spx_hip_matvec_trans_mode(const spx_matrix_t *A)
+try {
+    return A && A->dev ? device_trans_mode(A->dev) : -1;
+} SPX_C_BOUNDARY(return -1;)
 
 spx_error_t spx_hip_matvec_parts(spx_value_t alpha, const spx_matrix_t *A, const spx_value_t *x_dev,
                                  spx_value_t beta, spx_value_t *y_dev, int parts, void *stream, int *launched)

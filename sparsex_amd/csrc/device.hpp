@@ -28,6 +28,17 @@ void device_free(DeviceMatrix *m);
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream);
 
+// y <- alpha*A^T*x + beta*y on device pointers (d_x: nrows doubles, global rows for a row slice; d_y: ncols),
+// asynchronous on `stream`, no allocation.  Symmetric matrices run device_spmv.  General ones: csx_spmv_t_kernel
+// (spmv_t_kernels.hip) over the same stream, results through atomics; a row slice yields this process' partial
+// vector over all columns.  The caller keeps attached general matrices away.
+void device_spmv_trans(DeviceMatrix *m, double alpha, const double *d_x, double beta,
+                       double *d_y, void *stream);
+// spx.gpu.trans_windows as read where the device copy is built (0 false, 1 true, -1 auto) / what it came to:
+// 0 symmetric, 1 one atomic per nonzero, 2 unit windows accumulate in LDS
+void device_set_trans_windows(DeviceMatrix *m, int mode);
+int device_trans_mode(const DeviceMatrix *m);
+
 // Y <- alpha*A*X + beta*Y for nvec vectors at once (column-major: vector j of X at d_X + j * ldx, of Y at
 // d_Y + j * ldy); column j is what device_spmv writes for it.  Groups of device_mv_group(m) vectors share one
 // pass over the stream (spmv_mv_kernels.hip); asynchronous on `stream`, no allocation.

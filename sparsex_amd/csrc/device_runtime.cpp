@@ -2,7 +2,7 @@
 // (DeviceMatrix, device_upload), the choice of kernel for a product and its launches, the product in parts,
 // the host-vector entry point with its staging copies, page-locking, download, peek / poke and info.
 // Plain C++ on the HIP runtime API; the kernels and their launchers are in spmv_kernels.hip,
-// spmv_xw_kernels.hip and spmv_sx_kernels.hip (spmv_launch.hpp).
+// spmv_xw_kernels.hip, spmv_sx_kernels.hip and spmv_t_kernels.hip (spmv_launch.hpp).
 #include "device.hpp"
 #include "hip_check.hpp"
 #include "spmv_launch.hpp"
@@ -136,6 +136,11 @@ struct DeviceMatrix {
     bool xw_on = false;           // the product runs through csx_spmv_xw_kernel
     uint64_t xw_elems = 0, xw_unit_elems = 0, xw_staged = 0;
     size_t xw_rowblocks = 0;
+    // the transposed product (device_spmv_trans, csx_spmv_t_kernel): whether its unit passes accumulate in the
+    // unit windows (spx.gpu.trans_windows and the plan above), and the LDS of such a launch: the most rows
+    // (rounded up to even) + unit windows of a row-block
+    bool trans_xw = false;
+    uint32_t trans_lds_doubles = 0;
     // the read-once passes pipelined (sxplan.hpp; symmetric streams of row segments without tiles): a second set
     // of pass headers for csx_spmv_sx_kernel and the number of SX passes at the head of every row-block
     SpxPass *passes_sx = nullptr;
@@ -479,6 +484,9 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
         try {
             XwPlan plan;
             plan_unit_xwindows(s, ncols, s.xw_budget, s.xw_gap, plan, host_threads());
+            for (size_t i = 0; i < s.rbs.size(); ++i)
+                m->trans_lds_doubles = std::max(m->trans_lds_doubles, (((uint32_t) s.rbs[i].n_rows + 1u) & ~1u) +
+                                                                          plan.tab[i * XW_TAB].off_len);
             if (!m->launch_order.empty()) {
                 // (row-blocks and their headers went up in launch order: the window table and the headers follow;
                 // the descriptors stay where they are -- a row-block finds them through its desc_off)
@@ -515,6 +523,7 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
                 m->xw_rowblocks = plan.n_rb_windows;
                 m->xw_on = s.xw_on;
                 if ((size_t) m->lds_doubles_xw * sizeof(double) > 64u * 1024u) spmv_xw_allow_lds(160u * 1024u);
+                if ((size_t) m->trans_lds_doubles * sizeof(double) > 64u * 1024u) spmv_t_allow_lds(160u * 1024u);
                 log_msg(LOG_INFO, "unit windows: %zu of %zu row-blocks, %.1f %% of the unit nonzeros read x from LDS, "
                         "%.2f doubles staged per such nonzero, %u KB of LDS per workgroup\n", plan.n_rb_windows, plan.n_rb_units,
                         100.0 * (double) plan.unit_elems_lds / (double) std::max<uint64_t>(plan.unit_elems, 1),
@@ -637,6 +646,53 @@ void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream_)
 {
     device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, nullptr);
+}
+
+// y <- alpha*A^T*x + beta*y.  A symmetric matrix is its own transpose: the forward product, with everything it
+// means for slices and attached matrices.  A general one: beta * y over all columns, then one launch of
+// csx_spmv_t_kernel per launch of the forward product (column phases, slices in one launch and plain streams
+// alike), every one of which adds.  No fix-up, no carry; nothing allocated, nothing synchronised.
+// (a row slice reads its own rows of x and leaves this process' partial vector over all columns)
+void device_spmv_trans(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_)
+{
+    if (m->symmetric) {
+        device_spmv(m, alpha, d_x, beta, d_y, stream_);
+        return;
+    }
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+    m->launched_since_edit = true;
+    if (m->ncols) launch_scale(stream_, 1, d_y, 0, 0, m->ncols, beta);
+    const bool windows = m->trans_xw && m->passes_xw;
+    TransArgs a{};
+    a.rbs = m->rbs; a.values = m->values; a.cidx = m->cidx; a.segrows = m->segrows;
+    a.passes = windows ? m->passes_xw : m->passes;
+    a.descs = windows ? m->xdescs : m->descs;
+    a.xw_tab = windows ? m->xw_tab : nullptr;
+    a.x = d_x; a.y = d_y; a.alpha = alpha; a.pass_stride = m->pass_stride;
+    const size_t lds = (windows ? (size_t) m->trans_lds_doubles : (((size_t) m->mv_rows + 1u) & ~(size_t) 1)) * sizeof(double);
+    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
+        const uint32_t blocks = 8u * m->xcd_longest[ph];
+        if (blocks) launch_spmv_t(windows, m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// spx.gpu.trans_windows, resolved where the device copy is built: 0 = false, 1 = true, -1 = auto (windows where
+// the plan stages fewer doubles than it serves nonzeros: the atomic bytes of the two forms)
+void device_set_trans_windows(DeviceMatrix *m, int mode)
+{
+    m->trans_xw = m->passes_xw && !m->symmetric && (mode == 1 || (mode < 0 && m->xw_staged < m->xw_elems));
+}
+
+// -1 is the caller's (no device copy); 0: symmetric, the forward product runs; 1: one atomic per nonzero;
+// 2: unit windows accumulate in LDS
+int device_trans_mode(const DeviceMatrix *m)
+{
+    if (m->symmetric) return 0;
+    return m->trans_xw && m->passes_xw ? 2 : 1;
 }
 
 // (atomic hand-over of the tiles' sums: every row may be added to by several workgroups, so beta*y and the

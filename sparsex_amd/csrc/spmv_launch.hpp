@@ -1,6 +1,6 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the five interpreter translation
-// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_mv_kernels.hip,
+// XCD-aware row-block order, the kernel families and the launchers of the six interpreter translation
+// units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_t_kernels.hip, spmv_mv_kernels.hip,
 // spmv_mvsym_kernels.hip).  Plain C++: no
 // HIP header, so that the host runtime (device_runtime.cpp) is compiled by the host compiler.
 #pragma once
@@ -93,6 +93,22 @@ void spmv_sx_allow_lds(size_t bytes);
 // spmv_xw_kernels.hip
 void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs);
 void spmv_xw_allow_lds(size_t bytes);
+
+// spmv_t_kernels.hip: the transposed product of a general stream, y += alpha * A^T * x (every launch adds: the
+// caller has put beta * y there).  x: the rows of the matrix (global row numbers), y: its columns.
+struct TransArgs : StreamArgs {
+    const double *x;
+    double *y;
+    double alpha;
+    uint32_t pass_stride;
+    const XwEntry *xw_tab;   // `windows` launches: the table of the window plan; passes and descs are the plan's too
+};
+// `windows`: unit passes with SPX_PASSF_XLDS accumulate in the row-block's unit windows in LDS, which go to y once
+// (lds_bytes: the most rows of a row-block, rounded up to even, plus its unit windows); else one atomic per nonzero
+// (lds_bytes: the most rows of a row-block)
+void launch_spmv_t(bool windows, int waves, unsigned blocks, size_t lds_bytes, void *stream, const TransArgs &a,
+                   const XcdSplit &xs);
+void spmv_t_allow_lds(size_t bytes);
 
 // spmv_mv_kernels.hip: the multi-vector product, K = 2, 4 or 8 vectors per pass over the plain stream.
 // Column-major blocks: vector j of X at x + j * ldx, of Y at y + j * ldy.
