@@ -1,7 +1,9 @@
 """Cases that drive the fields of the row-block stream (sparsex_amd/csrc/gpu_format.h) to the upper end of
 their ranges: column offsets of 16, 24 and 32 bits, the 7-bit step of a unit descriptor, its 13 bits of
 "segments in front", the pass count of a row-block around the branch points of the kernels' pass loop, and
-the transposed-sum slots of the symmetric path.  test_limit_cases.py tunes every case host-only and asserts,
+the transposed-sum slots of the symmetric path; and what the multi-vector kernel of the read-once symmetric
+passes (spx.gpu.sym_matmat) adds to those: every width of a read-once segment, wide offsets in a row-block with
+slots, streams of a default tune restored with the option.  test_limit_cases.py tunes every case host-only and asserts,
 on the decoded stream, that it reaches the limit named here; test_gpu_stream_limits.py runs the same tunes
 through every kernel family that decodes the field.  No pytest code in here.
 
@@ -11,6 +13,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from sparsex_amd import synth
+import matmat_sym_cases as msc
 from stream_decode import Stream
 
 NOSAMPLE = {"spx.preproc.sampling": "none"}
@@ -112,11 +115,13 @@ def off_options(family, waves=4):
 
 
 # symmetric: the leftovers of the lower triangle of ONE row-block span the width
-def sym_wide(n, span, late=300, ends=24, seed=11):
+def sym_wide(n, span, late=300, ends=24, seed=11, runs=False):
     """n x n symmetric: a diagonal, and `late` last rows with four nonzeros each, uniform over columns
     (3, 3 + span); `ends` of them, chosen at random, also hold column 3, as many others column 3 + span.  Few
     enough (fewer than the 64 leftovers an x window needs) and irregular enough (no vertical unit) to stay
-    leftovers: the leftovers of the row-blocks of the late rows span `span` columns exactly."""
+    leftovers: the leftovers of the row-blocks of the late rows span `span` columns exactly.  `runs`: every late
+    row r also holds the three columns from span + 40 + 8 * ((7 r) % 50) on, behind the span and in front of
+    the late rows: read-once segments (with slots: 50 groups of eight columns) next to the wide leftovers."""
     rng = np.random.RandomState(seed)
     assert span + 16 < n - late
     r = np.repeat(np.arange(n - late, n), 4)
@@ -124,6 +129,11 @@ def sym_wide(n, span, late=300, ends=24, seed=11):
     pick = rng.choice(late, 2 * ends, replace=False)
     r = np.concatenate([r, n - late + pick])
     c = np.concatenate([c, np.full(ends, 3), np.full(ends, 3 + span)])
+    if runs:
+        assert span + 40 + 8 * 49 + 3 <= n - late
+        rr = np.arange(n - late, n)
+        r = np.concatenate([r, np.repeat(rr, 3)])
+        c = np.concatenate([c, (span + 40 + 8 * ((7 * rr) % 50)[:, None] + np.arange(3)[None, :]).ravel()])
     return _symmetric(r, c, n, rng)
 
 
@@ -358,6 +368,44 @@ SYM_CASES = {
 }
 
 
+# ---- symmetric path, several vectors per pass (spx.gpu.sym_matmat, csx_spmv_mvsym_kernel) --------------------
+# The cases above that reach a limit in the read-once passes or next to them, and two of this kernel's own:
+# read-once segments of every width (mvsym_seg_pass<W, K>, W = 2 .. 8), and 24-bit leftovers in a row-block
+# with slots (the ordinary passes of this kernel see a header whose rows are the slots and the y tile together).
+# name -> (generator, options on top of the family's)
+SYM_MATMAT_CASES = {
+    "step-127-sym": SYM_CASES["step-127-sym"][:2],
+    "slots-3072": SYM_CASES["slots-3072"][:2],
+    "slots-wide-cap": SYM_CASES["slots-wide-cap"][:2],
+    "noslot": SYM_CASES["noslot"][:2],
+    "passes-edge-sym": SYM_CASES["passes-edge-sym"][:2],
+    "seg-widths": (msc.seg_widths, {}),
+    "off-sym-3-runs": (lambda: sym_wide(70000, 65536, runs=True), {}),
+}
+SEG_WIDTHS = set(range(2, 9))
+NVECS_SYM = (2, 3, 5, 8, 13, 15)            # (in one call 15 is 8 + 4 + 2 + 1 where the group is eight)
+# the streams a default tune leaves, restored with the option: wide row-blocks, which the tune with it never emits
+# (seg-widths on top of the four the limits call for: every width in row-blocks of up to 990 rows, group 4)
+SYM_MATMAT_RESTORED = ("step-127-sym", "noslot", "slots-3072", "slots-wide-cap", "seg-widths")
+# what test_limit_cases.py asks of these streams and the emitter's choices keep out of reach, with the line: nothing
+SYM_MATMAT_UNREACHABLE = {}
+
+
+def sym_matmat_on(case, waves=4):
+    """SYM_MATMAT_ON: tuned with the option (no row-block of more than 512 rows, atomic hand-over)."""
+    o = sym_options("segments", SYM_MATMAT_CASES[case][1])
+    o.update({"spx.gpu.sym_matmat": "true", "spx.gpu.wave_tiles": "false", "spx.gpu.waves": str(waves)})
+    return o
+
+
+def sym_matmat_default(case, waves=4):
+    """SYM_MATMAT_DEFAULT: what a tune without the option emits -- the hand-over pinned (spx.gpu.sym_spill=auto
+    is a measurement at tune time), and the wavefront count."""
+    o = sym_options("segments", SYM_MATMAT_CASES[case][1])
+    o.update({"spx.gpu.sym_spill": "atomic", "spx.gpu.waves": str(waves)})
+    return o
+
+
 # ---- what a saved stream holds ----------------------------------------------------------------------------
 
 def census(path, rows_from=0):
@@ -366,7 +414,8 @@ def census(path, rows_from=0):
     s = Stream(path)
     out = {"widths": set(), "steps": {}, "front": 0, "seg0": 0, "n_pass": 0, "n_slots": 0, "noslot": 0,
            "elem0_front": 0, "pass_counts": set(), "kinds": set(), "symseg_steps": {}, "rows": 0,
-           "wide_slots": 0, "wide_noslot": 0}
+           "wide_slots": 0, "wide_noslot": 0, "symseg_widths": set(), "symseg_inline": 0, "symseg_listed": 0,
+           "rowblocks": []}
     for rb in s.rbs[s.rbs["row0"] >= rows_from]:
         ps = s.passes[int(rb["pass_off"]):int(rb["pass_off"]) + int(rb["n_pass"])]
         out["pass_counts"].add(int(rb["n_pass"]))
@@ -377,6 +426,8 @@ def census(path, rows_from=0):
         if wide:
             out["wide_slots"] = max(out["wide_slots"], int(rb["n_slots"]))
         out["kinds"] |= set(ps["kind"].tolist())
+        # (rows, slots, width of the offsets, pass kinds) of every row-block
+        out["rowblocks"].append((int(rb["n_rows"]), int(rb["n_slots"]), int(rb["cidx_width"]), set(ps["kind"].tolist())))
         if (ps["kind"] == PASS_GATHER).any():
             out["widths"].add(int(rb["cidx_width"]))
         for p in ps:
@@ -396,6 +447,8 @@ def census(path, rows_from=0):
                 tab = out["symseg_steps"] if sym else out["steps"]
                 tab[k] = max(tab.get(k, 0), st)
             if sym:
+                out["symseg_widths"].add(int(p["width"]))
+                out["symseg_inline" if int(p["flags"]) & 1 else "symseg_listed"] += 1
                 none = int((s.descs["col0"][rank + 1] == 0xFFFFFFFF).sum())       # (rank: per lane)
                 out["noslot"] += none
                 out["wide_noslot"] += none if wide else 0

@@ -1,7 +1,8 @@
 """Cases and helpers shared by the tests of the multi-vector product on symmetric streams whose values are read
 once (spx.gpu.sym_matmat; test_matmat_sym_host.py on the CPU, test_gpu_matmat_sym.py on the GPU): symmetric
 matrices that make the emitter produce tiles, read-once segments, both, segments without a slot, rows shared
-between row-blocks and a core small enough for a group of eight; and what a saved stream must look like."""
+between row-blocks and a core small enough for a group of eight; and what a saved stream must look like.
+seg_widths and expected_mvsym_group also serve the limit cases (limit_cases.py, test_gpu_stream_limits.py)."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -94,6 +95,23 @@ def block_banded():
     return _symmetric(8 * nb, *_blocks(np.concatenate(bi), np.concatenate(bj)), seed=9)
 
 
+SEG_WIDTHS_N, SEG_WIDTHS_FIRST = 4096, 1024
+
+
+def seg_widths(width=None):
+    """n = 4096: every row r >= 1024 holds one run in front of the diagonal, 2 + (r // 128) % 11 columns wide (2 to
+    12, the same for 128 rows in turn; the emitter cuts a run of more than eight columns into chunks), starting at
+    column 8 * ((5 r) % 64) + r % 3: read-once segments of every width the kernels are instantiated for.  `width`:
+    that width in every row instead (what test_limit_cases.py regenerates the case with, to see its check fail)."""
+    n = SEG_WIDTHS_N
+    rows = np.arange(SEG_WIDTHS_FIRST, n)
+    wid = 2 + (rows // 128) % 11 if width is None else np.full(rows.size, width)
+    start = 8 * ((5 * rows) % 64) + rows % 3
+    r = np.repeat(rows, wid)
+    c = np.repeat(start, wid) + (np.arange(r.size) - np.repeat(np.cumsum(wid) - wid, wid))
+    return _symmetric(n, r, c, seed=10)
+
+
 def _from_synth(csr):
     rp, ci, va, n = csr
     return csr, sp.csr_matrix((va, ci, rp), shape=(n, n))
@@ -128,6 +146,27 @@ def slotless_groups(s):
             rank = np.unique(int(ps["rank0"]) + 2 * np.cumsum(starts))
             n += int((s.descs[d0 + rank + 1]["col0"] == NO_SLOT).sum())
     return n
+
+
+MVSYM_LDS_BUDGET = 80 * 1024      # of device_runtime.cpp, in bytes
+
+
+def expected_mvsym_group(s):
+    """The group a device copy of the stream `s`, tuned or restored under spx.gpu.sym_matmat=true with one tile per
+    workgroup, serves (sparsex_hip.h, device_mv_group of device_runtime.cpp): 1 unless the stream is symmetric, hands
+    over with atomics and holds read-once passes; else the widest K of 8, 4, 2 of which that many copies of
+    {slots, y tile} of the largest row-block, and the first columns of the slot groups of the one with the most
+    slots, fit 80 KB of LDS; 1 where not even two do."""
+    if not (s.symmetric and s.sym_atomic and len(s.rbs)):
+        return 1
+    if not np.isin(s.passes["kind"], (PASS_SYMTILE, PASS_SYMSEG)).any():
+        return 1
+    core = int((s.rbs["n_rows"].astype(np.int64) + s.rbs["n_slots"]).max())
+    groups = (int(s.rbs["n_slots"].max()) + 7) // 8
+    for K in (8, 4, 2):
+        if K * core * 8 + groups * 4 <= MVSYM_LDS_BUDGET:
+            return K
+    return 1
 
 
 def check_stream_fits(path, m):

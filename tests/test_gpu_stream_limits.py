@@ -1,8 +1,9 @@
 """The kernels at the limits of the row-block stream's fields (sparsex_amd/csrc/gpu_format.h): the cases of
 limit_cases.py -- column offsets of 16, 24 and 32 bits, steps of 127, up to 8188 segments in front of a unit,
 pass counts at the branch points of the pass loop, full sets of transposed-sum slots and lanes without one --
-through every kernel family that decodes the field.  test_limit_cases.py proves on the CPU that each tune used
-here reaches its limit.  Every product is checked with helpers.check_y (matmat_cases.check_y_rect for the
+through every kernel family that decodes the field, the multi-vector kernel of the read-once symmetric passes
+(spx.gpu.sym_matmat) among them: tuned with the option, and on default-tuned streams restored with it.
+test_limit_cases.py proves on the CPU that each tune used here reaches its limit.  Every product is checked with helpers.check_y (matmat_cases.check_y_rect for the
 rectangular ones): `mult` on a y of NaN, the alpha / beta kernel, NaN behind x and y on the device."""
 import numpy as np
 import pytest
@@ -13,6 +14,8 @@ from sparsex_amd import synth
 from helpers import tune
 import limit_cases as lc
 import matmat_cases as mc
+import matmat_sym_cases as msc
+from stream_decode import Stream
 
 pytestmark = pytest.mark.gpu
 
@@ -179,6 +182,89 @@ def test_symmetric_offsets_of_32_bits(shared, family):
     A = _load(csr, m, dict(lc.sym_options(family), **{"spx.gpu.waves": "4"}), sym=True)
     products(torch, shared, A, m, host=False, beta=family == "lists")
     A.destroy()
+
+
+# ---- 2b. symmetric path, several vectors per pass -----------------------------------------------------------
+# csx_spmv_mvsym_kernel (spx.gpu.sym_matmat): K = 2, 4 or 8 vectors per pass over a stream with read-once passes.
+# Every column against the CSR product (matmat_cases.run: helpers.check_y, NaN behind every vector, a Y of NaN
+# where beta = 0); the columns go through atomics, nothing is compared bit for bit.  The group is never
+# hard-coded: it is what matmat_sym_cases.expected_mvsym_group makes of the saved stream.
+
+def _stream_group(A, tmp_path):
+    f = str(tmp_path / "group.spx")
+    A.save(f)
+    return msc.expected_mvsym_group(Stream(f))
+
+
+def _matmat_runs(torch, A, m, nvecs=lc.NVECS_SYM):
+    """The vector counts with the (alpha, beta) pairs in turn; ldx = columns + 1 or + 2: odd in every second run
+    at least, where every second vector of X is 8-byte aligned only."""
+    for k, nvec in enumerate(nvecs):
+        alpha, beta = mc.ALPHA_BETA[k % 3]
+        mc.run(torch, A, m, nvec, alpha, beta, padx=1 + k % 2, pady=5 if k % 2 else 2)
+
+
+def _sym_matmat_case(torch, shared, tmp_path, case, waves):
+    gen, _ = lc.SYM_MATMAT_CASES[case]
+    csr, m = shared.matrix(case, gen)
+    A = _load(csr, m, lc.sym_matmat_on(case, waves), sym=True)
+    inf = A.info()
+    assert inf.symmetric and inf.waves == waves and inf.sym_segments > 0 and not inf.wave_tiles
+    g = A.matmat_group()
+    print("%s tuned with spx.gpu.sym_matmat, %d wavefronts: group %d" % (case, waves, g))
+    assert g == _stream_group(A, tmp_path)
+    _matmat_runs(torch, A, m)
+    A.destroy()
+
+
+@pytest.mark.parametrize("case", list(lc.SYM_MATMAT_CASES))
+def test_symmetric_matmat_limits(shared, tmp_path, case):
+    """Tuned with the option, 4 wavefronts: read-once segments of every width 2 .. 8 with slots (seg-widths) and
+    without, inline descriptors and listed ones (noslot) -- groups of eight, so that 15 vectors run K = 8, 4
+    and 2 --, the chain with row and column step 127, 24-bit leftovers next to slots, full sets of slots."""
+    import torch
+    _sym_matmat_case(torch, shared, tmp_path, case, 4)
+
+
+@pytest.mark.parametrize("waves", lc.PASS_WAVES)
+def test_symmetric_matmat_pass_counts(shared, tmp_path, waves):
+    """The pass loop of mvsym_body at its branch points.  (A launch of more than 40 KB of LDS runs eight
+    wavefronts whatever the tune says: the groups of two run at the tune's count.)"""
+    import torch
+    _sym_matmat_case(torch, shared, tmp_path, "passes-edge-sym", waves)
+
+
+@pytest.mark.parametrize("case", lc.SYM_MATMAT_RESTORED)
+def test_symmetric_matmat_restored(shared, tmp_path, case):
+    """A stream from a tune WITHOUT the option (row-blocks of up to 2048 rows), restored with it: the option is
+    read at restore time and the group is what the stream's largest row-block leaves room for -- 1 for
+    slots-wide-cap, whose product then runs column by column.  Restored without the option: group 1."""
+    import torch
+    gen, _ = lc.SYM_MATMAT_CASES[case]
+    csr, m = shared.matrix(case, gen)
+    H = tune(csr, lc.sym_matmat_default(case), sym=True, host_only=True)
+    f = str(tmp_path / "default.spx")
+    H.save(f)
+    H.destroy()
+    s = Stream(f)
+    want = msc.expected_mvsym_group(s)
+    assert int(s.rbs["n_rows"].max()) > 512
+    assert (want == 1) == (case == "slots-wide-cap")
+    sx.options_reset()
+    sx.option_set("spx.gpu.sym_matmat", "true")
+    B = sx.mat_restore(f)
+    print("%s restored with spx.gpu.sym_matmat: group %d, largest row-block %d rows, largest core %d doubles" % (
+        case, B.matmat_group(), int(s.rbs["n_rows"].max()),
+        int((s.rbs["n_rows"].astype(np.int64) + s.rbs["n_slots"]).max())))
+    assert B.info().symmetric and B.info().waves == 4
+    assert B.matmat_group() == want
+    _matmat_runs(torch, B, m)
+    B.destroy()
+    sx.options_reset()
+    C = sx.mat_restore(f)
+    assert C.matmat_group() == 1
+    _matmat_runs(torch, C, m, nvecs=(3, 8))
+    C.destroy()
 
 
 # ---- 3. steps, segments in front, pass counts: general path -------------------------------------------------

@@ -280,6 +280,57 @@ def test_no_plan_no_windows(shared, opts):
     trans_runs(shared, A, mat, pairs=mc.ALPHA_BETA[:1])
 
 
+@pytest.fixture(scope="module")
+def saved_cant(shared, tmp_path_factory):
+    """cant tuned with the module's options, with the unit windows forced on and without a window plan, each saved.
+    All three tunes see the default spx.gpu.trans_windows (auto): the option is not part of the file."""
+    mat = shared.matrix("cant", CASES["cant"][0])
+    d = tmp_path_factory.mktemp("trans")
+    files, windows = {}, {}
+    for key, more in (("measured", {}), ("plan", {"spx.gpu.unit_windows": "true"}),
+                      ("no-plan", {"spx.gpu.unit_windows": "false"})):
+        A = tune(mat[0], dict(NOSAMPLE, **more))
+        files[key] = str(d / (key + ".spx"))
+        A.save(files[key])
+        windows[key] = A.info().unit_windows        # (what the launch tuner settled on goes into the file)
+        A.destroy()
+    sx.options_reset()
+    assert windows["plan"] == 1 and windows["no-plan"] == 0
+    return mat, files, windows
+
+
+@pytest.mark.parametrize("tw", ["false", "true", "auto"])
+def test_restored_matrix_reads_the_option_at_restore_time(shared, saved_cant, tw):
+    """spx.gpu.trans_windows is read where the device copy is built: a file restored under each value adds the way
+    THAT value says, and multiplies right.  A restored matrix plans the unit windows only where its forward product
+    was saved with them on (a tuned one always plans them unless told not to): the file of the default tune holds
+    them or not by what the launch tuner measured, so the file with spx.gpu.unit_windows=true is the one that shows
+    modes 1, 2 and 2; a file without a plan adds per nonzero whatever the option."""
+    mat, files, windows = saved_cant
+    for key in ("measured", "plan"):
+        sx.options_reset()
+        sx.option_set(TW, tw)
+        B = sx.mat_restore(files[key])
+        inf = B.info()
+        print("%s restored, trans_windows=%s: mode %d, plan %s, staged %d, window nonzeros %d" % (
+            key, tw, B.trans_mode(), "yes" if inf.unit_window_lds else "no", inf.unit_window_staged, inf.unit_window_elems))
+        assert (inf.unit_window_lds > 0) == (windows[key] == 1)
+        assert B.trans_mode() == expected_mode(B, tw)
+        if key == "plan":
+            # (cant stages fewer doubles than its windows serve nonzeros: test_auto_counts_atomic_bytes)
+            assert B.trans_mode() == (1 if tw == "false" else 2)
+        trans_runs(shared, B, mat)
+        B.destroy()
+    if tw == "true":
+        sx.options_reset()
+        sx.option_set(TW, tw)
+        B = sx.mat_restore(files["no-plan"])
+        assert B.info().unit_window_lds == 0 and B.trans_mode() == 1
+        trans_runs(shared, B, mat, pairs=mc.ALPHA_BETA[:2])
+        B.destroy()
+    sx.options_reset()
+
+
 # ---- 3. symmetric tunes ----------------------------------------------------------------------------------------
 
 SYM_CASES = {

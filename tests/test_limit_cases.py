@@ -12,6 +12,8 @@ import sparsex_amd as sx
 from helpers import tune
 import limit_cases as lc
 import matmat_cases as mc
+import matmat_sym_cases as msc
+from stream_decode import PASS, RB
 
 
 def _tune(csr, m, opts, sym=False):
@@ -308,3 +310,85 @@ def test_which_symmetric_cases_the_pipeline_takes(case):
     heads, n_sx, count = A.sym_pipeline()
     print("%s: %s" % (case, count))
     assert (count["rowblocks_with_sx"] > 0) == pipelined
+
+
+# ---- symmetric path, several vectors per pass -----------------------------------------------------------------
+
+def _sym_matmat_census(tmp_path, case, opts, gen=None):
+    csr, m = (gen or lc.SYM_MATMAT_CASES[case][0])()
+    c, s, A = _decoded(tmp_path, csr, m, opts, sym=True)
+    A.destroy()
+    c["group"] = msc.expected_mvsym_group(s)
+    c["wide"] = [rb for rb in c["rowblocks"] if rb[0] > 512]
+    return c, s
+
+
+def _check_sym_matmat(case, mode, c):
+    """What the stream of `case` under `mode` ("on": tuned with spx.gpu.sym_matmat, "default": without) must hold
+    for its runs in test_gpu_stream_limits.py to reach the limit it is there for."""
+    widths, steps = c["symseg_widths"], c["symseg_steps"]
+    if mode == "on":
+        assert c["rows"] <= 512                         # (the tune with the option emits no wide row-block)
+    if case == "noslot" and mode == "on":
+        assert widths >= lc.SEG_WIDTHS and c["symseg_inline"] > 0 and c["symseg_listed"] > 0
+        assert c["noslot"] >= 100 and c["group"] == 8
+    if case == "seg-widths" and mode == "on":
+        assert widths >= lc.SEG_WIDTHS and c["symseg_inline"] == 0 and c["noslot"] == 0 and c["group"] == 8
+    if case == "seg-widths" and mode == "default":
+        # (not asked of a restored stream, but there: every width in row-blocks of more than 512 rows)
+        assert widths >= lc.SEG_WIDTHS and c["wide"] and c["group"] >= 2
+    if case == "step-127-sym":
+        assert steps.get(3) == 127
+        if mode == "default":
+            assert c["wide"] and c["group"] >= 2
+    if case == "passes-edge-sym" and mode == "on":
+        assert c["pass_counts"] >= set(lc.PASS_COUNTS) and lc.PASS_SYMSEG in c["kinds"] and c["group"] >= 2
+    if case == "off-sym-3-runs" and mode == "on":
+        assert any(w == 3 and slots > 0 and {lc.PASS_GATHER, lc.PASS_SYMSEG} <= kinds
+                   for rows, slots, w, kinds in c["rowblocks"])
+    if case == "slots-3072" and mode == "default":
+        assert any(slots == 3072 for rows, slots, w, kinds in c["wide"]) and c["n_slots"] == 3072
+        assert lc.PASS_GATHER_LDS in c["kinds"] and c["group"] == 2
+    if case == "slots-wide-cap" and mode == "default":
+        assert any(rows == 2048 and slots == 8192 for rows, slots, w, kinds in c["wide"]) and c["group"] == 1
+    if case == "noslot" and mode == "default":
+        assert c["wide"] and c["group"] >= 2
+
+
+@pytest.mark.parametrize("case", list(lc.SYM_MATMAT_CASES))
+def test_symmetric_matmat_streams(tmp_path, case):
+    """Tuned with the option and without it (the stream that test_gpu_stream_limits.py restores with it): the
+    matrix exactly, and the limit the case is run for."""
+    for mode, opts in (("on", lc.sym_matmat_on(case)), ("default", lc.sym_matmat_default(case))):
+        c, s = _sym_matmat_census(tmp_path, case, opts)
+        print("%s %s: group %d, rows %d, core %d, read-once widths %s (%d inline, %d not), %d lanes without a slot, "
+              "steps %s, %d wide row-blocks" % (
+                  case, mode, c["group"], c["rows"], max(rb[0] + rb[1] for rb in c["rowblocks"]),
+                  sorted(c["symseg_widths"]), c["symseg_inline"], c["symseg_listed"], c["noslot"], c["symseg_steps"],
+                  len(c["wide"])))
+        assert s.symmetric and s.sym_atomic
+        _check_sym_matmat(case, mode, c)
+    assert set(lc.SYM_MATMAT_RESTORED) <= set(lc.SYM_MATMAT_CASES)
+    assert not lc.SYM_MATMAT_UNREACHABLE
+
+
+def test_symmetric_matmat_checks_bite(tmp_path):
+    """seg-widths regenerated with runs of three columns only no longer passes its check; the expected group
+    follows the core (a group of 8 needs 8 x core x 8 B + 4 B per slot group within 80 KB)."""
+    c, s = _sym_matmat_census(tmp_path, "seg-widths", lc.sym_matmat_on("seg-widths"), gen=lambda: msc.seg_widths(3))
+    assert c["symseg_widths"] == {3}
+    with pytest.raises(AssertionError):
+        _check_sym_matmat("seg-widths", "on", c)
+
+    class Fake:
+        symmetric, sym_atomic = 1, 1
+        passes = np.zeros(1, dtype=PASS)
+
+        def __init__(self, rows, slots):
+            self.rbs = np.zeros(1, dtype=RB)
+            self.rbs["n_rows"], self.rbs["n_slots"] = rows, slots
+    Fake.passes["kind"] = lc.PASS_SYMSEG
+    cores = ((512, 760), (512, 768), (1024, 8), (64, 1752), (930, 3072), (2048, 8192), (512, 3072))
+    assert [msc.expected_mvsym_group(Fake(r, sl)) for r, sl in cores] == [8, 4, 8, 4, 2, 1, 2]
+    Fake.passes["kind"] = lc.PASS_GATHER
+    assert msc.expected_mvsym_group(Fake(64, 0)) == 1
