@@ -539,6 +539,72 @@ typedef struct {
     uint64_t sym_passes, sx_passes;
 } spx_hip_sx_plan_t;
 spx_error_t spx_hip_mat_sym_pipeline(spx_matrix_t *A, spx_hip_sx_plan_t *plan);
+
+/* New values, same pattern: the outer loop of a Newton method, a time stepper or an interior-point solver keeps
+ * the sparsity pattern and changes every value.  Instead of a new tune, or one spx_mat_set_entry per nonzero
+ * (all the reference offers, src/api/matvec.c:376-407), the tuned stream is tied to the caller's CSR arrays
+ * ONCE (spx_hip_mat_values_plan, host side) and every outer iteration gathers the new value array into the
+ * stream in one bandwidth-bound pass (spx_hip_mat_set_values: csx_refresh_values_kernel).
+ *
+ *  - Which arrays: rowptr, colind and the value arrays are the ones given to spx_input_load_csr for this
+ *    matrix -- the same rows (the slice's rows for an input loaded with spx.rt.row_offset, the whole matrix
+ *    with spx.rt.gpu_rank/world), the same indexing (SPX_INDEX_ZERO_BASED / SPX_INDEX_ONE_BASED), columns of a
+ *    row in any order the loader accepts.
+ *  - A matrix tuned with SPX_MAT_REORDER or spx.rt.dist_reorder is addressed in the caller's numbering: the plan
+ *    goes through the inverse of the matrix' permutation.
+ *  - Symmetric matrices: the stream holds the entries on and below the diagonal of the tuned numbering; the plan
+ *    takes each from exactly the CSR position the tune read, from the transposed position where that one is
+ *    absent.  The caller's values must be symmetric.
+ *  - Every stored copy is written: lower triangle, mirror image, the thin mirror list of a slice, the diagonal
+ *    array, every column slice of spx.gpu.col_phases.
+ *  - A process of a row-partitioned matrix plans the entries its own stream holds.
+ *  - The plan fails with SPX_FAILURE through the error handler, the first offending (row, column) named, unless
+ *    every CSR entry the process owns has at least one destination and every real position of the stream has a
+ *    source: a pattern that is not the tuned one, a row with a repeated column, an entry the tune did not
+ *    keep.  A failed call leaves no plan behind (the values stay as they are).
+ *  - Positions without a source -- pass padding, lanes beyond a segment's length, absent cells of an 8x8 tile,
+ *    the zero a dense block of a symmetric stream holds where it closes over the diagonal (the diagonal has an
+ *    array of its own) -- hold, after any number of updates, exactly the bits the tune put there.
+ *  - spx_hip_mat_set_values only enqueues on `stream` (a hipStream_t): no allocation, no wait, legal during
+ *    stream capture.  It obeys the handle's single-stream rule: the stream orders it with the matrix' products.
+ *    `values_dev` holds as many doubles as the planned CSR arrays hold entries, in HBM of the matrix' device.
+ *  - It counts as "a product was enqueued since the last edit" for spx_mat_set_entry's wait-once rule; after it
+ *    spx_mat_get_entry, spx_mat_set_entry, spx_mat_save and every product (forward, transposed, multi-vector,
+ *    in parts, distributed) see the new values.
+ *  - spx_hip_mat_set_values_host takes a host array and is synchronous: on a matrix in HBM the array goes up into
+ *    a temporary buffer in pieces through page-locked staging, the kernel runs, the buffer is freed; on a
+ *    host-only matrix (spx.rt.host_only) the host threads apply the plan to the host copy of the stream.
+ *  - The values of the encoded partitions (spx_hip_mat_export_csx) are stale after a bulk update: from the first
+ *    successful spx_hip_mat_set_values* on, spx_hip_mat_export_csx fails and says so -- it never hands out old
+ *    values.  spx_hip_mat_export_units (the pattern) keeps working.  While they are stale spx_mat_set_entry leaves
+ *    them alone and spx_mat_save writes the file without them: a matrix restored from it has none to export.  (A
+ *    host-only matrix knows when spx_hip_mat_set_values_host has put back, bit for bit, the values it held before
+ *    the first update: its partitions are true again, exported again and saved again.)
+ *  - spx_hip_mat_values_plan leaves the calling thread's current device as it found it.
+ *  - The plan is not part of a saved matrix: after spx_mat_restore it is built again from the CSR arrays (a
+ *    restored matrix, which may hold no encoded partitions, works like a tuned one).  A second
+ *    spx_hip_mat_values_plan replaces the first; spx_hip_mat_values_plan_drop and spx_mat_destroy release it.
+ *  - spx_hip_mat_set_values* fail with SPX_FAILURE without a plan, with a NULL handle or pointer, when the
+ *    calling thread's current device is not the matrix' one, and spx_hip_mat_set_values on a host-only matrix.
+ *  - Cost: one uint32_t per stored value (spx_index_t is 32-bit, so a CSR index fits) in HBM and once more on the
+ *    host -- about half of value_bytes, 3 GB on a matrix of 769 M nonzeros.  */
+spx_error_t spx_hip_mat_values_plan(spx_matrix_t *A, const spx_index_t *rowptr, const spx_index_t *colind, int indexing);
+spx_error_t spx_hip_mat_values_plan_drop(spx_matrix_t *A);
+spx_error_t spx_hip_mat_set_values(spx_matrix_t *A, const spx_value_t *values_dev, void *stream);
+spx_error_t spx_hip_mat_set_values_host(spx_matrix_t *A, const spx_value_t *values);
+/* The plan, for inspection and tests: the arrays belong to the matrix and live until the next
+ * spx_hip_mat_values_plan, spx_hip_mat_values_plan_drop or spx_mat_destroy(). */
+typedef struct {
+    const uint32_t *src_values;   /* per position of the stream's values: CSR index, or 0xffffffff (no source) */
+    const uint32_t *src_mirror;   /* per entry of the thin mirror list of a symmetric slice                    */
+    const uint32_t *src_diag;     /* symmetric: per own row, CSR index of its diagonal entry or 0xffffffff      */
+    size_t n_values, n_mirror, n_diag;
+    uint64_t n_sources;           /* CSR entries this process' stream holds at least once                      */
+    uint64_t n_dest;              /* positions with a source, over the three arrays                            */
+    uint64_t plan_bytes;          /* HBM the plan occupies (0 on a host-only matrix)                           */
+} spx_hip_values_plan_t;
+spx_error_t spx_hip_mat_values_plan_get(const spx_matrix_t *A, spx_hip_values_plan_t *plan);
+
 /* The same for a caller compiled against another revision of this header: at most `size` bytes
  * (the caller's sizeof(spx_hip_info_t)) are written -- the struct only ever grows at its end.
  * spx_hip_mat_info() writes sizeof(spx_hip_info_t) of THIS header; SPX_HIP_ABI_VERSION changes

@@ -61,6 +61,13 @@ class SxPlan(C.Structure):
                 ("sx_elems", C.c_uint64), ("sym_passes", C.c_uint64), ("sx_passes", C.c_uint64)]
 
 
+class ValuesPlan(C.Structure):
+    _fields_ = [("src_values", C.POINTER(C.c_uint32)), ("src_mirror", C.POINTER(C.c_uint32)),
+                ("src_diag", C.POINTER(C.c_uint32)), ("n_values", C.c_size_t), ("n_mirror", C.c_size_t),
+                ("n_diag", C.c_size_t), ("n_sources", C.c_uint64), ("n_dest", C.c_uint64),
+                ("plan_bytes", C.c_uint64)]
+
+
 class XwPlan(C.Structure):
     _fields_ = [("tab", C.POINTER(C.c_uint32)), ("xdescs", C.POINTER(C.c_uint32)), ("passes", C.c_void_p),
                 ("n_rowblocks", C.c_size_t), ("n_descs", C.c_size_t), ("n_passes", C.c_size_t),
@@ -158,6 +165,11 @@ def lib():
     L.spx_hip_matvec_trans_kernel_vec.argtypes = [d, vp, vp, d, vp, vp]
     L.spx_hip_matvec_trans_mode.restype = C.c_int
     L.spx_hip_matvec_trans_mode.argtypes = [vp]
+    L.spx_hip_mat_values_plan.argtypes = [vp, vp, vp, i]
+    L.spx_hip_mat_values_plan_drop.argtypes = [vp]
+    L.spx_hip_mat_set_values.argtypes = [vp, vp, vp]
+    L.spx_hip_mat_set_values_host.argtypes = [vp, vp]
+    L.spx_hip_mat_values_plan_get.argtypes = [vp, C.POINTER(ValuesPlan)]
     L.spx_log_disable_all.restype = None
     L.spx_log_error_console.restype = None
     _lib = L
@@ -479,6 +491,83 @@ class Matrix:
                                      C.c_double(value), C.c_int(indexing))
         if rc != SPX_SUCCESS:
             raise SpxError("entry (%d, %d) not set" % (row, col))
+
+    def values_plan(self, rowptr, colind, indexing=SPX_INDEX_ZERO_BASED):
+        """``spx_hip_mat_values_plan`` -- ties the tuned stream to the CSR arrays the matrix was loaded from
+        (int32 numpy arrays), once; `set_values` then takes every new value array."""
+        rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+        ci = np.ascontiguousarray(colind, dtype=np.int32)
+        if rp.ndim != 1 or ci.ndim != 1 or rp.size < 1 or ci.size < int(rp[-1]) - int(rp[0]):
+            raise SpxError("values_plan: rowptr / colind are not CSR arrays")
+        rc = lib().spx_hip_mat_values_plan(self.handle, rp.ctypes.data, ci.ctypes.data if ci.size else rp.ctypes.data,
+                                           indexing)
+        if rc != SPX_SUCCESS:
+            self._plan_nnz = None
+            raise SpxError("spx_hip_mat_values_plan failed (see stderr)")
+        self._plan_nnz = int(rp[-1]) - int(rp[0])
+
+    def values_plan_drop(self):
+        """``spx_hip_mat_values_plan_drop``."""
+        self._plan_nnz = None
+        if lib().spx_hip_mat_values_plan_drop(self.handle) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_values_plan_drop failed")
+
+    def values_plan_info(self):
+        """``spx_hip_mat_values_plan_get`` as numpy copies: src_values / src_mirror / src_diag (uint32,
+        0xffffffff = no source) and the counters n_sources, n_dest, plan_bytes."""
+        pl = ValuesPlan()
+        L = lib()
+        if L.spx_hip_mat_values_plan_get(self.handle, C.byref(pl)) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_values_plan_get failed: no plan")
+        out = {k: int(getattr(pl, k)) for k in ("n_values", "n_mirror", "n_diag", "n_sources", "n_dest", "plan_bytes")}
+        for name, n in (("src_values", pl.n_values), ("src_mirror", pl.n_mirror), ("src_diag", pl.n_diag)):
+            out[name] = np.ctypeslib.as_array(getattr(pl, name), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        return out
+
+    def hip_set_values(self, ptr, stream=0):
+        """``spx_hip_mat_set_values`` -- the planned CSR value array, in HBM at `ptr`, gathered into the stream on
+        `stream` (enqueue only)."""
+        if lib().spx_hip_mat_set_values(self.handle, ptr, stream) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_set_values failed (see stderr)")
+
+    def set_values(self, values, stream=None):
+        """New values for the planned pattern: a 1-D contiguous float64 array as long as the planned CSR arrays.
+        A torch tensor on the matrix' HIP device takes the device path (``spx_hip_mat_set_values`` on `stream`,
+        default the current torch stream); a numpy array the host path (``spx_hip_mat_set_values_host``,
+        synchronous; also for host-only matrices)."""
+        want = getattr(self, "_plan_nnz", None)
+        if isinstance(values, np.ndarray):
+            if values.dtype != np.float64:
+                raise SpxError("set_values: values must be float64, not %s" % values.dtype)
+            if values.ndim != 1 or not values.flags["C_CONTIGUOUS"]:
+                raise SpxError("set_values: values must be a contiguous 1-D array")
+            if want is None:
+                raise SpxError("set_values: no values plan (call values_plan first)")
+            if values.size != want:
+                raise SpxError("set_values: %d values for a plan of %d entries" % (values.size, want))
+            keep = values if values.size else np.zeros(1)
+            if lib().spx_hip_mat_set_values_host(self.handle, keep.ctypes.data) != SPX_SUCCESS:
+                raise SpxError("spx_hip_mat_set_values_host failed (see stderr)")
+            return
+        import torch
+        if not isinstance(values, torch.Tensor):
+            raise SpxError("set_values: a numpy array or a torch tensor, not %s" % type(values).__name__)
+        if values.dtype != torch.float64:
+            raise SpxError("set_values: values must be float64, not %s" % values.dtype)
+        if values.dim() != 1 or (values.shape[0] > 1 and values.stride(0) != 1):
+            raise SpxError("set_values: values must be a contiguous 1-D tensor")
+        if want is None:
+            raise SpxError("set_values: no values plan (call values_plan first)")
+        if values.shape[0] != want:
+            raise SpxError("set_values: %d values for a plan of %d entries" % (values.shape[0], want))
+        if values.device.type != "cuda":
+            raise SpxError("set_values: a tensor must live on the matrix' HIP device, not on %s (hand a numpy array "
+                           "to the host path)" % values.device)
+        inf = self.info()
+        if inf.on_device and values.device.index != inf.device:
+            raise SpxError("the matrix lives on cuda:%d, the values on %s" % (inf.device, values.device))
+        st = stream if stream is not None else torch.cuda.current_stream(values.device)
+        self.hip_set_values(values.data_ptr(), st.cuda_stream)
 
     def get_perm(self):
         """``spx_mat_get_perm`` -- perm[old index] = new index of a matrix tuned with

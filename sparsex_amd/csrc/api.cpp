@@ -1017,6 +1017,7 @@ static spx_matrix_t *do_tune(spx_input_t *in)
     A->dev = nullptr;
     A->host_only = host_only;
     A->device_ordinal = (int) cfg.get_long("spx.rt.device");
+    A->input_row_base = slice_rows > 0 ? (int64_t) slice_off : -1;
 
     const size_t nown = last - first;
     std::vector<std::ostringstream> logs(nown);
@@ -1575,7 +1576,11 @@ try {
         SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
         return SPX_FAILURE;
     }
-    if (!A->parts.empty()) {
+    if (A->values_refreshed) {
+        // (a bulk update has left the encoded partitions behind: they stay as they are, spx_hip_mat_export_csx
+        // refuses them, and no later update can make them true again)
+        A->edited_while_stale = true;
+    } else if (!A->parts.empty()) {
         // the encoded partitions follow (export in the reference's layout)
         build_spans(A);
         val_t *v = locate_encoded(A, row, column);
@@ -1747,7 +1752,10 @@ try {
     h.n_spill = gs->n_spill;
     h.lds_doubles = gs->lds_doubles;
     h.waves = gs->waves;
-    h.n_encoded = (uint32_t) A->parts.size();
+    // (encoded partitions whose values a bulk update has left behind are not written: a restored matrix must not
+    // export them, spx_hip_mat_set_values)
+    const size_t n_encoded = A->values_refreshed ? 0 : A->parts.size();
+    h.n_encoded = (uint32_t) n_encoded;
     h.sym_atomic = gs->sym_atomic ? 1u : 0u;
     // (bit 2: the product runs with the unit windows of x in LDS; bits 8-15 / 16-31: their gap and budget)
     h.pad3 = (gs->deterministic ? 1u : 0u) | (gs->wave_tiles ? 2u : 0u);
@@ -1772,7 +1780,7 @@ try {
     good = good && put_vec(f, perm);
     // the encoded partitions, where they are still held: a restored matrix can
     // then be exported in the reference's CSX layout like the one that was saved
-    for (size_t i = 0; good && i < A->parts.size(); ++i)
+    for (size_t i = 0; good && i < n_encoded; ++i)
         good = put_partition(f, A->parts[i], A->symmetric ? &A->diag[i] : nullptr);
     good = (fclose(f) == 0) && good;
     if (!good) {
@@ -1869,6 +1877,9 @@ try {
     A->dev = nullptr;
     A->waves = (h.waves == 2 || h.waves == 8) ? (int) h.waves : 4;
     A->own_lo = h.own_lo; A->own_hi = h.own_hi;
+    // (a process that holds every partition but not every row was tuned from a row slice: spx_hip_mat_values_plan)
+    if (h.first_part == 0 && h.last_part == h.nr_partitions && (h.own_lo > 0 || h.own_hi < h.nrows))
+        A->input_row_base = h.own_lo;
     A->nnz_stored = h.nnz_stored; A->n_unit_elems = h.n_unit_elems;
     A->n_delta_elems = h.n_delta_elems; A->n_units = h.n_units;
     A->value_bytes = gs->values.size() * sizeof(val_t);
@@ -2428,6 +2439,155 @@ try {
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
+// ---- new values, same pattern --------------------------------------------------------------------------
+// The reference changes a tuned matrix entry by entry (spx_mat_set_entry, src/api/matvec.c:376-407).  An outer
+// loop that keeps the pattern and changes every value ties the stream to its CSR arrays once (values_plan.cpp)
+// and then gathers every new value array in one pass (refresh_kernels.hip).
+
+spx_error_t spx_hip_mat_values_plan(spx_matrix_t *A, const spx_index_t *rowptr, const spx_index_t *colind, int indexing)
+try {
+    if (!A || !rowptr || !colind) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    const GpuStream *s = A->host_stream ? A->host_stream.get() : A->index.get();
+    if (!s) { SETERROR_1(SPX_ERR_TUNED_MAT, "matrix holds no descriptor stream"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    try {
+        ValuesPlanInput in;
+        in.stream = s;
+        in.n_values = A->host_stream ? A->host_stream->values.size() : device_n_values(A->dev);
+        in.nrows = (size_t) A->nrows;
+        in.ncols = (size_t) A->ncols;
+        in.symmetric = A->symmetric != 0;
+        in.own_lo = (size_t) A->own_lo;
+        in.own_hi = (size_t) A->own_hi;
+        in.perm = A->permutation != SPX_INVALID_PERM ? A->permutation : nullptr;
+        in.rowptr = rowptr;
+        in.colind = colind;
+        in.base = indexing == SPX_INDEX_ONE_BASED ? 1 : 0;
+        // the arrays of spx_input_load_csr: the whole matrix, or the rows of a slice loaded with spx.rt.row_offset
+        in.csr_row_base = A->input_row_base >= 0 ? (size_t) A->input_row_base : 0;
+        in.csr_rows = A->input_row_base >= 0 ? (size_t) A->own_hi - in.csr_row_base : (size_t) A->nrows;
+        std::unique_ptr<ValuesPlan> plan(new ValuesPlan);
+        build_values_plan(in, *plan, host_threads());
+        size_t bytes = 0;
+        if (A->dev) bytes = device_values_plan_set(A->dev, *plan);
+        A->values_plan = std::move(plan);
+        A->values_plan_bytes = bytes;
+    } catch (const FatalError &e) {
+        // (no plan is left behind, an earlier one included; the values stay as they are)
+        if (A->dev) device_values_plan_drop(A->dev);
+        A->values_plan.reset();
+        A->values_plan_bytes = 0;
+        SETERROR_1(SPX_ERR_ARG_INVALID, e.what.c_str());
+        return SPX_FAILURE;
+    } catch (const std::exception &e) {
+        if (A->dev) device_values_plan_drop(A->dev);
+        A->values_plan.reset();
+        A->values_plan_bytes = 0;
+        SETERROR_1(SPX_ERR_MEM_ALLOC, e.what());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_values_plan_drop(spx_matrix_t *A)
+try {
+    if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    if (A->dev) device_values_plan_drop(A->dev);
+    A->values_plan.reset();
+    A->values_plan_bytes = 0;
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+// what follows a bulk update on the host side: the encoded partitions no longer show the matrix
+static void values_were_refreshed(spx_matrix_t *A)
+{
+    A->values_refreshed = true;
+    A->exported.clear();
+    A->exported_rows_info.clear();
+}
+
+spx_error_t spx_hip_mat_set_values(spx_matrix_t *A, const spx_value_t *values_dev, void *stream)
+try {
+    if (!A || !values_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    if (!A->dev) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "matrix was tuned with spx.rt.host_only=true: no HIP executor "
+                   "(spx_hip_mat_set_values_host takes a host array)");
+        return SPX_FAILURE;
+    }
+    if (!A->values_plan) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "no values plan: call spx_hip_mat_values_plan first");
+        return SPX_FAILURE;
+    }
+    try {
+        device_set_values(A->dev, values_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    if (!A->values_refreshed) {
+        std::lock_guard<std::mutex> lk(A->mtx);
+        values_were_refreshed(A);
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_set_values_host(spx_matrix_t *A, const spx_value_t *values)
+try {
+    if (!A || !values) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    if (!A->values_plan) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "no values plan: call spx_hip_mat_values_plan first");
+        return SPX_FAILURE;
+    }
+    bool as_before = false;
+    try {
+        if (A->host_stream) {
+            // (the values are at hand: remember what the first update replaces, and notice when one puts it back --
+            // the encoded partitions, which hold exactly that, are then true again)
+            if (!A->values_refreshed && !A->parts.empty()) {
+                A->pre_refresh_digest = values_plan_digest(*A->values_plan, *A->host_stream, host_threads());
+                A->has_pre_refresh_digest = true;
+                A->edited_while_stale = false;
+            }
+            apply_values_plan(*A->values_plan, values, *A->host_stream, host_threads());
+            as_before = A->has_pre_refresh_digest && !A->edited_while_stale &&
+                        values_plan_digest(*A->values_plan, *A->host_stream, host_threads()) == A->pre_refresh_digest;
+        } else if (A->dev) {
+            device_set_values_host(A->dev, values, A->values_plan->csr_nnz);
+        } else {
+            throw FatalError("matrix holds no descriptor stream");
+        }
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    if (as_before) A->values_refreshed = false;
+    else values_were_refreshed(A);
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_values_plan_get(const spx_matrix_t *A, spx_hip_values_plan_t *out)
+try {
+    if (!A || !out) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    if (!A->values_plan) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "no values plan: call spx_hip_mat_values_plan first");
+        return SPX_FAILURE;
+    }
+    const ValuesPlan &p = *A->values_plan;
+    memset(out, 0, sizeof(*out));
+    out->src_values = p.src_values.data();
+    out->src_mirror = p.src_mirror.data();
+    out->src_diag = p.src_diag.data();
+    out->n_values = p.src_values.size();
+    out->n_mirror = p.src_mirror.size();
+    out->n_diag = p.src_diag.size();
+    out->n_sources = p.n_sources;
+    out->n_dest = p.n_dest;
+    out->plan_bytes = A->values_plan_bytes;
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
 spx_error_t spx_hip_mat_info_sized(const spx_matrix_t *A, void *info, size_t size)
 try {
     spx_hip_info_t full;
@@ -2507,6 +2667,11 @@ try {
         return SPX_FAILURE;
     }
     std::lock_guard<std::mutex> lk(A->mtx);
+    if (A->values_refreshed) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "the values of the encoded partitions are stale: the matrix took new values "
+                   "through spx_hip_mat_set_values (spx_hip_mat_export_units still shows the pattern)");
+        return SPX_FAILURE;
+    }
     size_t li = (size_t) part - A->first_part;
     if (A->exported.size() < A->parts.size()) {
         A->exported.resize(A->parts.size());

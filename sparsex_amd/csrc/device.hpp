@@ -142,6 +142,21 @@ double device_peek(const DeviceMatrix *m, bool diagonal, size_t index);
 void device_poke(DeviceMatrix *m, bool diagonal, size_t index, double value);
 void device_poke_mirror(DeviceMatrix *m, size_t index, double value);   // GpuStream::mirror_val
 
+// New values, same pattern (values_plan.hpp).  device_values_plan_set uploads the three source arrays of a plan
+// (replacing an earlier one) and returns the HBM they take; device_set_values gathers the caller's CSR value
+// array (in HBM, `csr_nnz` doubles) into the stream's values, mirror list and diagonal: it only enqueues on
+// `stream` -- no allocation, no wait, legal during stream capture -- and counts as a product for device_poke's
+// wait-once rule.  device_set_values_host takes the array from host memory: a temporary HBM buffer filled in
+// pieces through page-locked staging, the same kernels, a wait, the buffer freed.  Both setters refuse a calling
+// thread whose current device is not the matrix' one; device_values_plan_set works on the matrix' device and
+// leaves the current device as it found it.
+struct ValuesPlan;
+size_t device_values_plan_set(DeviceMatrix *m, const ValuesPlan &plan);
+void device_values_plan_drop(DeviceMatrix *m);
+void device_set_values(DeviceMatrix *m, const double *d_csr_values, void *stream);
+void device_set_values_host(DeviceMatrix *m, const double *h_csr_values, size_t csr_nnz);
+size_t device_n_values(const DeviceMatrix *m);     // doubles in the stream's value array
+
 struct DeviceMatrixInfo {
     size_t n_rowblocks, n_shared_rows;
     size_t value_bytes, index_bytes;

@@ -10,6 +10,7 @@
 #include "stream_index.hpp"
 #include "sxplan.hpp"
 #include "threads.hpp"
+#include "values_plan.hpp"
 #include "xwindows.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -153,6 +154,11 @@ struct DeviceMatrix {
     std::vector<uint64_t> rb_xneed;
     size_t xneed_piece = 0;
     hipStream_t up_stream = nullptr;            // ... on a stream of its own
+    // new values, same pattern (values_plan.hpp): per position of values / mirror_val / per own row of dvalues the
+    // index in the caller's CSR value array (each padded to a multiple of four entries), and the array's length
+    uint32_t *plan_values = nullptr, *plan_mirror = nullptr, *plan_diag = nullptr;
+    size_t plan_n_diag = 0, plan_diag_lo = 0, plan_csr_nnz = 0, plan_bytes = 0;
+    bool has_plan = false;
 };
 
 // the multi-vector product (device_spmm): the widest group, and the LDS a workgroup of its kernels may take
@@ -615,6 +621,7 @@ void device_free(DeviceMatrix *m)
         if (m->mirror_col) (void) hipFree(m->mirror_col);
         if (m->mirror_val) (void) hipFree(m->mirror_val);
     }
+    device_values_plan_drop(m);
     if (m->passes_sx) (void) hipFree(m->passes_sx);
     if (m->sx_tab) (void) hipFree(m->sx_tab);
     if (m->passes_xw) (void) hipFree(m->passes_xw);
@@ -1566,6 +1573,124 @@ void device_poke(DeviceMatrix *m, bool diagonal, size_t index, double value)
     HIP_CHECK(hipMemcpy((diagonal ? m->dvalues : m->values) + index, &value, sizeof(value),
                         hipMemcpyHostToDevice));
 }
+
+// ---- new values, same pattern ---------------------------------------------------------------------------
+void device_values_plan_drop(DeviceMatrix *m)
+{
+    if (m->plan_values) (void) hipFree(m->plan_values);
+    if (m->plan_mirror) (void) hipFree(m->plan_mirror);
+    if (m->plan_diag) (void) hipFree(m->plan_diag);
+    m->plan_values = m->plan_mirror = m->plan_diag = nullptr;
+    m->plan_n_diag = m->plan_diag_lo = m->plan_csr_nnz = m->plan_bytes = 0;
+    m->has_plan = false;
+}
+
+size_t device_values_plan_set(DeviceMatrix *m, const ValuesPlan &plan)
+{
+    if (plan.src_values.size() != m->n_values || plan.src_mirror.size() != m->n_mirror_nnz ||
+        (!plan.src_diag.empty() && (!m->dvalues || plan.own_lo + plan.src_diag.size() > m->nrows)))
+        throw FatalError("values plan: not the plan of this stream");
+    // (on the matrix' device, and the caller's current device as it was afterwards)
+    int before = -1;
+    HIP_CHECK(hipGetDevice(&before));
+    struct Back {
+        int dev;
+        ~Back() { (void) hipSetDevice(dev); }
+    } back{before};
+    HIP_CHECK(hipSetDevice(m->device));
+    device_values_plan_drop(m);
+    // the stream's own upload path (Placement: allocated, cleared, copied).  The kernel reads the plan sixteen
+    // bytes at a time: every array gets room for a multiple of four entries, the ones behind its end without a source
+    const std::vector<uint32_t> *from[3] = {&plan.src_values, &plan.src_mirror, &plan.src_diag};
+    uint32_t **to[3] = {&m->plan_values, &m->plan_mirror, &m->plan_diag};
+    Placement place;
+    size_t bytes = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (from[k]->empty()) continue;
+        const size_t pad = (4 - from[k]->size() % 4) % 4;
+        place.put(to[k], *from[k], pad);
+        bytes += (from[k]->size() + pad) * sizeof(uint32_t);
+    }
+    try {
+        place.flush(m, false);
+        for (int k = 0; k < 3; ++k) {
+            const size_t n = from[k]->size(), pad = (4 - n % 4) % 4;
+            if (n && pad) HIP_CHECK(hipMemset(*to[k] + n, 0xff, pad * sizeof(uint32_t)));
+        }
+    } catch (...) {
+        device_values_plan_drop(m);
+        throw;
+    }
+    m->plan_n_diag = plan.src_diag.size();
+    m->plan_diag_lo = plan.own_lo;
+    m->plan_csr_nnz = plan.csr_nnz;
+    m->plan_bytes = bytes;
+    m->has_plan = true;
+    return bytes;
+}
+
+void device_set_values(DeviceMatrix *m, const double *d_csr_values, void *stream)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+    if (!m->has_plan) throw FatalError("no values plan: call spx_hip_mat_values_plan first");
+    m->launched_since_edit = true;
+    if (m->plan_values) launch_refresh_values(stream, m->values, m->plan_values, d_csr_values, m->n_values);
+    if (m->plan_mirror) launch_refresh_values(stream, m->mirror_val, m->plan_mirror, d_csr_values, m->n_mirror_nnz);
+    if (m->plan_diag) launch_refresh_values(stream, m->dvalues + m->plan_diag_lo, m->plan_diag, d_csr_values, m->plan_n_diag);
+}
+
+void device_set_values_host(DeviceMatrix *m, const double *h_csr_values, size_t csr_nnz)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+    if (!m->has_plan) throw FatalError("no values plan: call spx_hip_mat_values_plan first");
+    if (csr_nnz != m->plan_csr_nnz) throw FatalError("values plan: the value array is not as long as the planned one");
+    if (!m->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking));
+    hipStream_t st = m->host_stream;
+    const size_t bytes = csr_nnz * sizeof(double);
+    double *d = nullptr, *stage = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto release = [&]() {
+        if (d) (void) hipFree(d);
+        if (stage) (void) hipHostFree(stage);
+        for (hipEvent_t e : ev)
+            if (e) (void) hipEventDestroy(e);
+    };
+    try {
+        // two page-locked pieces take turns: the threads fill one while the DMA engine moves the other
+        const size_t piece = std::min(STAGE_PIECE, std::max<size_t>(bytes, 8));
+        HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), bytes ? bytes : 8));
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&stage), 2 * piece, hipHostMallocDefault));
+        for (hipEvent_t &e : ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        size_t turn = 0;
+        for (size_t off = 0; off < bytes; off += piece, ++turn) {
+            const size_t n = std::min(piece, bytes - off);
+            char *half = reinterpret_cast<char *>(stage) + (turn & 1) * piece;
+            if (turn >= 2) HIP_CHECK(hipEventSynchronize(ev[turn & 1]));
+            copy_threads(half, reinterpret_cast<const char *>(h_csr_values) + off, n);
+            HIP_CHECK(hipMemcpyAsync(reinterpret_cast<char *>(d) + off, half, n, hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipEventRecord(ev[turn & 1], st));
+        }
+        // (products a client enqueued on streams of its own are not ordered against this one: wait for them as
+        // device_poke does, once)
+        quiesce_before_edit(m);
+        device_set_values(m, d, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        m->launched_since_edit = false;
+    } catch (...) {
+        (void) hipStreamSynchronize(st);
+        release();
+        throw;
+    }
+    release();
+}
+
+size_t device_n_values(const DeviceMatrix *m) { return m->n_values; }
 
 void device_info(const DeviceMatrix *m, DeviceMatrixInfo &info)
 {

@@ -11,6 +11,7 @@
 #include "input.hpp"
 #include "xwindows.hpp"
 #include "sxplan.hpp"
+#include "values_plan.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -113,6 +114,18 @@ struct matrix {
     uint32_t xw_budget = 3072, xw_gap = 16;   // spx.gpu.unit_window_doubles, spx.gpu.unit_window_gap
     std::unique_ptr<spx::XwPlan> xw_inspect;    // what spx_hip_mat_unit_windows handed out last
     std::unique_ptr<spx::SxPlan> sx_inspect;    // ... and spx_hip_mat_sym_pipeline
+    // new values, same pattern (spx_hip_mat_values_plan, values_plan.hpp): the host copy of the plan, the HBM its
+    // copy takes, and whether a bulk update has left the encoded partitions' values behind (spx_hip_mat_export_csx)
+    std::unique_ptr<spx::ValuesPlan> values_plan;
+    size_t values_plan_bytes = 0;
+    bool values_refreshed = false;
+    // host-only matrices: the digest of the values held before the first bulk update (values_plan_digest), and
+    // whether a spx_mat_set_entry has come since -- it leaves stale partitions alone, so they cannot become true again
+    spx::ValuesDigest pre_refresh_digest;
+    bool has_pre_refresh_digest = false, edited_while_stale = false;
+    // the CSR input was a row slice (spx.rt.row_offset / spx.rt.global_rows): its first row, -1 = the whole matrix
+    // (a restored matrix: told from its partitions and own rows)
+    int64_t input_row_base = -1;
     int device_ordinal = -1;
     std::vector<std::vector<idx_t>> spans;    // per partition and row: reach of its units
     std::vector<idx_t> max_span;              // per partition

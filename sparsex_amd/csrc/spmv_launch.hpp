@@ -142,4 +142,9 @@ void launch_spmv_mvsym(int K, int waves, unsigned blocks, size_t lds_bytes, void
                        const XcdSplit &xs);
 void spmv_mvsym_allow_lds(size_t bytes);
 
+// refresh_kernels.hip: dst[i] = src[map[i]] for the n positions of a value array of the stream, where map[i] is
+// not 0xffffffff (values_plan.hpp).  `map` holds n rounded up to a multiple of four entries, the padding without a
+// source.  Enqueues on `stream`, nothing else.
+void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n);
+
 }  // namespace spx

@@ -1,6 +1,7 @@
 // stream_index.cpp -- see stream_index.hpp.
 #include "stream_index.hpp"
 
+#include "stream_lanes.hpp"
 #include "threads.hpp"
 
 #include <algorithm>
@@ -8,65 +9,6 @@
 #include <cstring>
 
 namespace spx {
-
-namespace {
-
-inline uint32_t popcount_upto(uint64_t mask, uint32_t lane)
-{
-    // set bits in lanes 1..lane (bit 0 is never set)
-    const uint64_t m = lane >= 63 ? mask : (mask & ((2ull << lane) - 1ull));
-    return (uint32_t) __builtin_popcountll(m);
-}
-
-struct LaneSeg { int64_t row; int64_t col0; int64_t dcol_elem; bool ok; };
-
-// row (relative to the row-block) and first column of lane l of a unit pass
-inline void unit_lane(const GpuStream &s, const SpxRowBlock &rb, const SpxPass &ps, uint32_t l,
-                      int64_t &row, int64_t &col, uint32_t *slot = nullptr)
-{
-    // (read-once symmetric segments: two entries per unit, the second holds the slot)
-    const uint32_t stride = ps.kind == SPX_PASS_SYMSEG ? 2u : 1u;
-    const uint32_t rank = (uint32_t) ps.rank0 + stride * popcount_upto(spx_pass_mask(&ps), l);
-    const SpxUnitDesc &d = s.descs[(size_t) rb.desc_off + rank];
-    if (slot) *slot = stride == 2 ? s.descs[(size_t) rb.desc_off + rank + 1].col0 : SPX_NO_SLOT;
-    const uint32_t bits = d.bits;
-    const int sidx = (int) ((ps.seg0 + l - ((bits >> 9) & 8191u)) & 0xffffu);
-    const uint32_t kind = (bits >> 22) & 7u;
-    const int step = (int) (bits >> 25);
-    const int drow = kind == SPX_KIND_BLOCK ? 1 : (kind >= SPX_KIND_VERT ? step : 0);
-    const int dcol = (kind == SPX_KIND_HORIZ || kind == SPX_KIND_DIAG)
-                         ? step : (kind == SPX_KIND_ADIAG ? -step : 0);
-    row = (int64_t) ps.elem0 + (int64_t) (bits & 511u) + (int64_t) sidx * drow;
-    col = (int64_t) d.col0 + (int64_t) sidx * dcol;
-    if (slot && *slot != SPX_NO_SLOT) *slot = (uint32_t)((int64_t) *slot + (int64_t) sidx * dcol);
-}
-
-// column of leftover e of a gather pass (through L2, or from the x window)
-inline int64_t gather_col(const GpuStream &s, const SpxRowBlock &rb, const SpxPass &ps, size_t e)
-{
-    if (ps.kind == SPX_PASS_GATHER_LDS) {
-        uint16_t v;
-        std::memcpy(&v, s.cidx.data() + ((size_t) rb.cidx_off + rb.near_off) * 16u + e * 2, 2);
-        return (int64_t) rb.xwin_base + v;
-    }
-    const uint8_t *c = s.cidx.data() + (size_t) rb.cidx_off * 16u;
-    if (rb.cidx_width == 4) {
-        uint32_t v;
-        std::memcpy(&v, c + e * 4, 4);
-        return (int64_t) rb.cbase + v;
-    }
-    uint16_t v;
-    std::memcpy(&v, c + e * 2, 2);
-    if (rb.cidx_width == 3) return (int64_t) rb.cbase + (v | ((uint32_t) c[(size_t) rb.hi_off * 16u + e] << 16));
-    return (int64_t) rb.cbase + v;
-}
-
-inline bool is_gather(const SpxPass &ps)
-{
-    return ps.kind == SPX_PASS_GATHER || ps.kind == SPX_PASS_GATHER_LDS;
-}
-
-}  // namespace
 
 void stream_locate(const GpuStream &s, idx_t row, idx_t col, std::vector<size_t> &out)
 {
@@ -103,10 +45,10 @@ void stream_locate(const GpuStream &s, idx_t row, idx_t col, std::vector<size_t>
                 }
             } else if (ps.kind == SPX_PASS_SYMTILE) {
                 for (uint32_t l = 0; l < nseg; ++l) {
-                    const SpxUnitDesc &d = s.descs[(size_t) rb.desc_off + ps.rank0 + (l >> 3)];
-                    const int64_t r = (int64_t) ps.elem0 + (int64_t) (d.bits & 511u) + (l & 7u);
+                    int64_t r, c0;
+                    tile_lane(s, rb, ps, l, r, c0);
                     if (r != rrel) continue;
-                    const int64_t w = (int64_t) col - (int64_t) d.col0;
+                    const int64_t w = (int64_t) col - c0;
                     if (w >= 0 && w < 8) out.push_back(vbase + spx_pass_value_index(l, (uint32_t) w, nseg, 8));
                 }
             } else {
@@ -139,9 +81,9 @@ void stream_touched_rows(const GpuStream &s, idx_t below, std::vector<idx_t> &ro
                 if (is_gather(ps)) {
                     r = SPX_SEGROW_ROW(s.segrows[(size_t) rb.seg_off + ps.seg0 + l]);
                 } else if (ps.kind == SPX_PASS_SYMTILE) {
-                    const SpxUnitDesc &d = s.descs[(size_t) rb.desc_off + ps.rank0 + (l >> 3)];
-                    r = (int64_t) ps.elem0 + (int64_t) (d.bits & 511u) + (l & 7u);
-                    const int64_t c = (int64_t) d.col0 + (l & 7u);   // the transposed tile's row
+                    int64_t c0;
+                    tile_lane(s, rb, ps, l, r, c0);
+                    const int64_t c = c0 + (l & 7u);                 // the transposed tile's row
                     if (c < (int64_t) below) mark[(size_t) c] = 1;
                 } else {
                     int64_t c;
@@ -181,10 +123,11 @@ void stream_read_cols(const GpuStream &s, idx_t own_lo, idx_t own_hi, size_t nco
                     for (uint32_t w = 0; w < W && w < SPX_SEGROW_LEN(sr); ++w)
                         hit(gather_col(s, rb, ps, (size_t) ps.elem0 + l + (size_t) w * nseg));
                 } else if (ps.kind == SPX_PASS_SYMTILE) {
-                    const SpxUnitDesc &d = s.descs[(size_t) rb.desc_off + ps.rank0 + (l >> 3)];
-                    for (uint32_t w = 0; w < 8; ++w) hit((int64_t) d.col0 + w);
+                    int64_t r, c0;
+                    tile_lane(s, rb, ps, l, r, c0);
+                    for (uint32_t w = 0; w < 8; ++w) hit(c0 + w);
                     // (the transposed products multiply x of the lane's own row)
-                    hit((int64_t) rb.row0 + (int64_t) ps.elem0 + (int64_t) (d.bits & 511u) + (l & 7u));
+                    hit((int64_t) rb.row0 + r);
                 } else {
                     int64_t r, c0;
                     unit_lane(s, rb, ps, l, r, c0);
