@@ -106,6 +106,11 @@
  *                           the window plan stages fewer doubles than it serves nonzeros) | "true" | "false" -- unit passes
  *                           accumulate in the row-block's unit windows in LDS, which are added to y once, instead of one
  *                           atomic add per nonzero; read by spx_mat_tune / spx_mat_restore, not saved with the matrix
+ *   spx.gpu.values_f32      "false" (default) | "true": a general tune keeps a float copy of the stream's values in HBM
+ *                           next to the doubles (half of value_bytes, an allocation of its own, also with
+ *                           spx.gpu.arena), built on the device once the launch tuner has settled, for
+ *                           spx_hip_matvec_kernel_f32; symmetric tunes ignore it; any other value fails the tune;
+ *                           read by spx_mat_tune / spx_mat_restore, not saved with the matrix
  *   spx.vec.device          "false" (default) | "true" (also: env SPX_VEC_DEVICE through spx_options_set_from_env):
  *                           vectors the library allocates itself (spx_vec_create, spx_vec_create_random; page-locked)
  *                           keep x's HBM copy between spx_matvec_* calls, reused while no spx_vec_* call has changed
@@ -203,6 +208,42 @@ spx_error_t spx_hip_matvec_trans_kernel(spx_value_t alpha, const spx_matrix_t *A
  * 0: symmetric, the forward product runs; 1: one atomic add per nonzero; 2: unit windows accumulate in LDS and
  * go to y once each (row-blocks and passes without windows still add per nonzero). */
 int spx_hip_matvec_trans_mode(const spx_matrix_t *A);
+
+/* ---- product with a float copy of the values ------------------------------------------
+ * y <- alpha*fl32(A)*x + beta*y on device memory, where fl32(A) holds A's stored entries rounded to float
+ * (nearest even).  For solvers that multiply with a rounded matrix most of the time (the correction step of
+ * iterative refinement, an inner or preconditioning Krylov solve) and with the exact one for the residual: both
+ * products run on ONE handle -- the same pattern, tune, descriptor stream and launch configuration; the float copy
+ * of the values (spx.gpu.values_f32=true at spx_mat_tune / spx_mat_restore, general matrices only) costs half of
+ * value_bytes of HBM and halves the value bytes a product reads.  Vectors stay fp64, every product and sum is
+ * fp64: the kernels load floats, widen them in registers and run the fp64 kernels' operations in their order.
+ * Semantics are those of spx_hip_matvec_kernel in every respect (rows written by a slice or an attached matrix,
+ * beta == 0 never reads y_dev, enqueues only, allocates nothing, hipGraph-capturable, the handle's single-stream
+ * rule -- the carry scratch is shared with the fp64 product --, counts as a product for spx_mat_set_entry's wait,
+ * bit-identical repeats under spx.gpu.deterministic=true); it runs the kernel family and wavefronts the handle's
+ * fp64 product runs.  Accuracy: within the fp64 bound of the exact product with fl32(A), hence within
+ * 2^-24 * |alpha| * sum|a||x| plus that bound of the product with A.  Stored values beyond float's range become
+ * +-inf in the copy, values below its normal range become subnormal or 0.
+ * spx_hip_mat_set_values(_host) writes both arrays in the same pass, spx_mat_set_entry patches the float next
+ * to the double; spx_mat_get_entry, spx_mat_save, export and every other product read the doubles, as without
+ * the option.
+ * SPX_FAILURE (through the error handler, nothing enqueued) for a NULL handle or pointer, overlapping x and y
+ * ranges, the wrong current device, a host-only matrix, (_vec) vectors whose sizes are not ncols / nrows, and a
+ * matrix WITHOUT a float copy -- tuned or restored without the option, or tuned as a symmetric one; the message
+ * says which.  There is no silent fp64 fallback.
+ * Not provided: float forms of the multi-vector, transposed, parts and dist products, host vectors, symmetric
+ * streams.
+ */
+spx_error_t spx_hip_matvec_mult_f32(spx_value_t alpha, const spx_matrix_t *A, const spx_value_t *x_dev,
+                                    spx_value_t *y_dev, void *stream);
+spx_error_t spx_hip_matvec_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, const spx_value_t *x_dev,
+                                      spx_value_t beta, spx_value_t *y_dev, void *stream);
+/* Bytes of HBM the float copy takes (4 per value of the stream, padding included); 0: no copy; -1: a NULL handle
+ * or a matrix without a device copy. */
+int64_t spx_hip_mat_values_f32_bytes(const spx_matrix_t *A);
+/* Diagnostic (tools/f32_bench.py): seconds one run of the kernel that builds the copy takes on this matrix
+ * (synchronous; rewrites the copy with what it holds); negative without a copy. */
+double spx_hip_mat_values_f32_narrow_seconds(const spx_matrix_t *A);
 
 /* ---- multi-vector product ----------------------------------------------------------
  * Y <- alpha*A*X + beta*Y for nvec vectors at once, on device memory.
@@ -305,6 +346,9 @@ spx_error_t spx_hip_probe_read_write(const spx_hip_vec_t *src, spx_hip_vec_t *ds
 spx_error_t spx_hip_matvec_kernel_vec(spx_value_t alpha, const spx_matrix_t *A,
                                       const spx_hip_vec_t *x, spx_value_t beta,
                                       spx_hip_vec_t *y, void *stream);
+/* y <- alpha*fl32(A)*x + beta*y on device vectors; see spx_hip_matvec_kernel_f32 */
+spx_error_t spx_hip_matvec_kernel_f32_vec(spx_value_t alpha, const spx_matrix_t *A, const spx_hip_vec_t *x,
+                                          spx_value_t beta, spx_hip_vec_t *y, void *stream);
 /* y <- alpha*A^T*x + beta*y on device vectors (x: nrows, y: ncols elements); see spx_hip_matvec_trans_kernel */
 spx_error_t spx_hip_matvec_trans_kernel_vec(spx_value_t alpha, const spx_matrix_t *A,
                                             const spx_hip_vec_t *x, spx_value_t beta,

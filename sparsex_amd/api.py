@@ -163,6 +163,13 @@ def lib():
     L.spx_hip_matvec_trans_mult.argtypes = [d, vp, vp, vp, vp]
     L.spx_hip_matvec_trans_kernel.argtypes = [d, vp, vp, d, vp, vp]
     L.spx_hip_matvec_trans_kernel_vec.argtypes = [d, vp, vp, d, vp, vp]
+    L.spx_hip_matvec_mult_f32.argtypes = [d, vp, vp, vp, vp]
+    L.spx_hip_matvec_kernel_f32.argtypes = [d, vp, vp, d, vp, vp]
+    L.spx_hip_matvec_kernel_f32_vec.argtypes = [d, vp, vp, d, vp, vp]
+    L.spx_hip_mat_values_f32_bytes.restype = C.c_int64
+    L.spx_hip_mat_values_f32_bytes.argtypes = [vp]
+    L.spx_hip_mat_values_f32_narrow_seconds.restype = C.c_double
+    L.spx_hip_mat_values_f32_narrow_seconds.argtypes = [vp]
     L.spx_hip_matvec_trans_mode.restype = C.c_int
     L.spx_hip_matvec_trans_mode.argtypes = [vp]
     L.spx_hip_mat_values_plan.argtypes = [vp, vp, vp, i]
@@ -320,6 +327,44 @@ class Matrix:
             raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, x.device))
         st = stream if stream is not None else torch.cuda.current_stream(y.device)
         self.hip_matvec_trans_kernel(alpha, x.data_ptr(), beta, y.data_ptr(), st.cuda_stream)
+        return y
+
+    def hip_matvec_kernel_f32(self, alpha, x_ptr, beta, y_ptr, stream=0):
+        """``spx_hip_matvec_kernel_f32``: y <- alpha*fl32(A)*x + beta*y on HBM pointers, with the float copy of
+        the values (spx.gpu.values_f32=true at tune or restore time); vectors, products and sums are fp64."""
+        rc = lib().spx_hip_matvec_kernel_f32(alpha, self.handle, x_ptr, beta, y_ptr, stream)
+        if rc != SPX_SUCCESS:
+            raise SpxError("spx_hip_matvec_kernel_f32 failed (see stderr)")
+
+    def values_f32_bytes(self):
+        """``spx_hip_mat_values_f32_bytes``: bytes of HBM the float copy of the values takes, 0 without one,
+        -1 for a matrix without a device copy."""
+        return int(lib().spx_hip_mat_values_f32_bytes(self.handle))
+
+    def matvec_f32(self, alpha, x, beta, y, stream=None):
+        """y <- alpha*fl32(A)*x + beta*y for 1-D contiguous torch float64 tensors on the matrix' device: x of ncols
+        elements, y of nrows.  `stream`: a torch stream (default: the current one of y's device).  Returns y."""
+        import torch
+        pairs = (("x", x, self.ncols), ("y", y, self.nrows))
+        for name, t, n in pairs:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a torch tensor" % name)
+            if t.dtype != torch.float64:
+                raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+            if t.dim() != 1 or t.shape[0] != n:
+                raise ValueError("%s must have the shape (%d,), not %s" % (name, n, tuple(t.shape)))
+            if t.shape[0] > 1 and t.stride(0) != 1:
+                raise ValueError("%s needs stride(0) == 1, not %d" % (name, t.stride(0)))
+        for name, t, n in pairs:
+            if t.device.type != "cuda":
+                raise ValueError("%s must live on the matrix' HIP device, not on %s" % (name, t.device))
+        if x.device != y.device:
+            raise ValueError("x and y live on different devices (%s, %s)" % (x.device, y.device))
+        inf = self.info()
+        if inf.on_device and x.device.index != inf.device:
+            raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, x.device))
+        st = stream if stream is not None else torch.cuda.current_stream(y.device)
+        self.hip_matvec_kernel_f32(alpha, x.data_ptr(), beta, y.data_ptr(), st.cuda_stream)
         return y
 
     def hip_matmat_kernel(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
@@ -705,6 +750,13 @@ def matvec_kernel_vec(A, alpha, x, beta, y, stream=0):
     rc = lib().spx_hip_matvec_kernel_vec(alpha, A.handle, x.handle, beta, y.handle, stream)
     if rc != SPX_SUCCESS:
         raise SpxError("spx_hip_matvec_kernel_vec failed (see stderr)")
+
+
+def matvec_kernel_f32_vec(A, alpha, x, beta, y, stream=0):
+    """``spx_hip_matvec_kernel_f32_vec``: y <- alpha*fl32(A)*x + beta*y on DeviceVectors (x: ncols, y: nrows)."""
+    rc = lib().spx_hip_matvec_kernel_f32_vec(alpha, A.handle, x.handle, beta, y.handle, stream)
+    if rc != SPX_SUCCESS:
+        raise SpxError("spx_hip_matvec_kernel_f32_vec failed (see stderr)")
 
 
 def matvec_trans_kernel_vec(A, alpha, x, beta, y, stream=0):

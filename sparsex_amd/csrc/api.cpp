@@ -964,6 +964,18 @@ static int read_trans_windows()
     return tw == "auto" ? -1 : (tw == "true" ? 1 : 0);
 }
 
+// spx.gpu.values_f32: a float copy of a general stream's values for spx_hip_matvec_kernel_f32.  Read where the
+// device copy is built, like spx.gpu.trans_windows; not saved with the matrix.
+static bool read_values_f32()
+{
+    const std::string v = Config::instance().get_str("spx.gpu.values_f32");
+    if (v != "true" && v != "false") {
+        log_msg(LOG_ERR, "spx.gpu.values_f32: true or false\n");
+        throw FatalError("bad spx.gpu.values_f32");
+    }
+    return v == "true";
+}
+
 static spx_matrix_t *do_tune(spx_input_t *in)
 {
     Config &cfg = Config::instance();
@@ -1188,6 +1200,7 @@ static spx_matrix_t *do_tune(spx_input_t *in)
     A->unit_windows = xw_mode == "auto" ? -1 : (xw_mode == "true" ? 1 : 0);
     A->xw_on = xw_mode == "true";                       // (auto: off until measured)
     A->trans_windows = read_trans_windows();
+    A->values_f32 = read_values_f32();
     const std::string sx_mode = cfg.get_str("spx.gpu.sym_pipeline");
     if (sx_mode != "auto" && sx_mode != "true" && sx_mode != "false") {
         log_msg(LOG_ERR, "spx.gpu.sym_pipeline: true, false or auto\n");
@@ -1276,6 +1289,10 @@ static spx_matrix_t *do_tune(spx_input_t *in)
         }
         log_msg(LOG_INFO, "column slices: %zu on XCD groups %.2f us, plain %.2f us per SpMV\n", K, 1e6 * t_ph, 1e6 * t_plain);
     }
+
+    // the float copy of the values, once, of the stream the tuners settled on (none of their trial uploads
+    // pays for it); symmetric tunes ignore the option
+    if (A->dev && A->values_f32 && !sym) device_build_values_f32(A->dev);
 
     if (!cfg.get_bool("spx.rt.keep_encoded")) {
         std::vector<Partition> *old = new std::vector<Partition>();
@@ -1916,6 +1933,7 @@ try {
     A->sym_matmat = gs->sym_matmat = A->symmetric && cfg.get_str("spx.gpu.sym_matmat") == "true";
     try {
         A->trans_windows = read_trans_windows();
+        A->values_f32 = read_values_f32();
     } catch (const FatalError &) {
         SETERROR_0(SPX_ERR_TUNED_MAT);
         return SPX_INVALID_MAT;
@@ -1929,6 +1947,7 @@ try {
             A->dev = device_upload(*gs, (size_t) A->nrows, (size_t) A->ncols, A->symmetric != 0,
                                    A->own_lo, A->own_hi, A->device_ordinal);
             device_set_trans_windows(A->dev, A->trans_windows);
+            if (A->values_f32 && !A->symmetric) device_build_values_f32(A->dev);
             keep_index(A.get(), std::move(*gs));
         } else {
             A->host_stream = std::move(gs);
@@ -2247,6 +2266,46 @@ try {
     }
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+// ---- the product with the float copy of the values (spx.gpu.values_f32) ----------------------------------
+spx_error_t spx_hip_matvec_mult_f32(spx_value_t alpha, const spx_matrix_t *A,
+                                    const spx_value_t *x_dev, spx_value_t *y_dev, void *stream)
+try {
+    return spx_hip_matvec_kernel_f32(alpha, A, x_dev, 0.0, y_dev, stream);
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_matvec_kernel_f32(spx_value_t alpha, const spx_matrix_t *A,
+                                      const spx_value_t *x_dev, spx_value_t beta,
+                                      spx_value_t *y_dev, void *stream)
+try {
+    if (check_dev(A, x_dev, y_dev) != SPX_SUCCESS) return SPX_FAILURE;
+    const uintptr_t x0 = (uintptr_t) x_dev, x1 = x0 + (size_t) A->ncols * sizeof(double);
+    const uintptr_t y0 = (uintptr_t) y_dev, y1 = y0 + (size_t) A->nrows * sizeof(double);
+    if (x0 < y1 && y0 < x1) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "vectors x and y overlap");
+        return SPX_FAILURE;
+    }
+    try {
+        device_spmv_f32(A->dev, alpha, x_dev, beta, y_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+int64_t spx_hip_mat_values_f32_bytes(const spx_matrix_t *A)
+try {
+    return A && A->dev ? device_values_f32_bytes(A->dev) : -1;
+} SPX_C_BOUNDARY(return -1;)
+
+// (diagnostic for tools/f32_bench.py: seconds of one run of csx_narrow_values_kernel over the stream's values;
+// negative where the matrix has no float copy)
+double spx_hip_mat_values_f32_narrow_seconds(const spx_matrix_t *A)
+try {
+    if (!A || !A->dev || device_values_f32_bytes(A->dev) <= 0) return -1.0;
+    return device_time_narrow_values(A->dev);
+} SPX_C_BOUNDARY(return -1.0;)
 
 int spx_hip_matvec_trans_mode(const spx_matrix_t *A)
 try {

@@ -28,6 +28,18 @@ void device_free(DeviceMatrix *m);
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream);
 
+// The float twin of the stream's values (spx.gpu.values_f32; general streams only): device_build_values_f32
+// allocates it (an allocation of its own, also with spx.gpu.arena) and fills it from the doubles in HBM with
+// csx_narrow_values_kernel -- synchronous, once per tune or restore, after the launch tuner has settled;
+// FatalError naming the size where HBM has no room.  device_values_f32_bytes: 4 bytes per stream value, 0 without
+// a twin.  device_spmv_f32: device_spmv with fl32(A) -- the handle's family and wavefronts, the kernels that
+// load floats; FatalError where there is no twin.  device_set_values and device_poke keep the twin true.
+void device_build_values_f32(DeviceMatrix *m);
+int64_t device_values_f32_bytes(const DeviceMatrix *m);
+double device_time_narrow_values(DeviceMatrix *m);     // seconds of one run of the narrowing kernel (tools)
+void device_spmv_f32(DeviceMatrix *m, double alpha, const double *d_x, double beta,
+                     double *d_y, void *stream);
+
 // y <- alpha*A^T*x + beta*y on device pointers (d_x: nrows doubles, global rows for a row slice; d_y: ncols),
 // asynchronous on `stream`, no allocation.  Symmetric matrices run device_spmv.  General ones: csx_spmv_t_kernel
 // (spmv_t_kernels.hip) over the same stream, results through atomics; a row slice yields this process' partial

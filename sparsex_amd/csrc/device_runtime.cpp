@@ -159,7 +159,13 @@ struct DeviceMatrix {
     uint32_t *plan_values = nullptr, *plan_mirror = nullptr, *plan_diag = nullptr;
     size_t plan_n_diag = 0, plan_diag_lo = 0, plan_csr_nnz = 0, plan_bytes = 0;
     bool has_plan = false;
+    // the float twin of `values` (spx.gpu.values_f32, general streams; device_build_values_f32): element i is
+    // values[i] rounded to nearest, tail slack included; an allocation of its own, also next to an arena
+    float *values_f32 = nullptr;
 };
+
+// elements behind the end of the stream's values that the pipelined kernels' paired loads may touch (never used)
+constexpr size_t VALUES_SLACK = 160;
 
 // the multi-vector product (device_spmm): the widest group, and the LDS a workgroup of its kernels may take
 // (two of them fit a CU's 160 KB)
@@ -442,7 +448,7 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
             if (!any) order.clear();
         }
         if (order.empty()) {
-            place.put(&m->values, s.values, 160);
+            place.put(&m->values, s.values, VALUES_SLACK);
             place.put(&m->descs, s.descs, 8);
             place.put(&m->rbs, s.rbs);
             place.put(&m->passes, s.passes, (size_t) s.pass_stride + 6 * MAX_WAVES_PER_BLOCK);
@@ -458,7 +464,7 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
                 std::copy(s.passes.begin() + (size_t) order[i] * stride, s.passes.begin() + ((size_t) order[i] + 1) * stride,
                           passes.begin() + i * stride);
             }
-            place.put(&m->values, s.values, 160);
+            place.put(&m->values, s.values, VALUES_SLACK);
             place.put(&m->descs, s.descs, 8);
             place.put(&m->rbs, rbs);
             place.put(&m->passes, passes, stride + 6 * MAX_WAVES_PER_BLOCK);
@@ -622,6 +628,7 @@ void device_free(DeviceMatrix *m)
         if (m->mirror_val) (void) hipFree(m->mirror_val);
     }
     device_values_plan_drop(m);
+    if (m->values_f32) (void) hipFree(m->values_f32);
     if (m->passes_sx) (void) hipFree(m->passes_sx);
     if (m->sx_tab) (void) hipFree(m->sx_tab);
     if (m->passes_xw) (void) hipFree(m->passes_xw);
@@ -647,12 +654,84 @@ struct SpmvPart {
     bool first, last;
 };
 static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
-                           size_t ldy, void *stream_, const SpmvPart *part);
+                           size_t ldy, void *stream_, const SpmvPart *part, bool f32 = false);
 
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream_)
 {
     device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, nullptr);
+}
+
+// ---- the float twin of the values ------------------------------------------------------------------------
+// Built from the doubles already in HBM (csx_narrow_values_kernel), once per tune or restore -- the caller
+// decides when: the trial uploads of a tune do not pay for it.  General streams only; synchronous.
+void device_build_values_f32(DeviceMatrix *m)
+{
+    if (m->symmetric) throw FatalError("float twin of the values: general streams only");
+    HIP_CHECK(hipSetDevice(m->device));
+    if (m->values_f32) {
+        (void) hipFree(m->values_f32);
+        m->values_f32 = nullptr;
+    }
+    // as many floats as `values` has room for doubles, to a multiple of four of them
+    const size_t n_alloc = (m->n_values + VALUES_SLACK + 3) & ~(size_t) 3;
+    const size_t n_narrow = (m->n_values + 3) & ~(size_t) 3;           // (within the doubles' slack; the rest stays 0)
+    void *d = nullptr;
+    if (hipMalloc(&d, n_alloc * sizeof(float)) != hipSuccess) {
+        (void) hipGetLastError();
+        log_msg(LOG_ERR, "spx.gpu.values_f32: no room in HBM for a float copy of the values (%zu bytes)\n", n_alloc * sizeof(float));
+        throw FatalError("spx.gpu.values_f32: cannot allocate " + std::to_string(n_alloc * sizeof(float)) +
+                         " bytes of HBM for the float copy of the values");
+    }
+    m->values_f32 = static_cast<float *>(d);
+    try {
+        HIP_CHECK(hipMemset(d, 0, n_alloc * sizeof(float)));
+        launch_narrow_values(nullptr, m->values_f32, m->values, n_narrow);
+        HIP_CHECK(hipDeviceSynchronize());
+    } catch (...) {
+        (void) hipFree(d);
+        m->values_f32 = nullptr;
+        throw;
+    }
+    // (the float kernels are allowed the dynamic LDS of their fp64 families where those are: spmv_allow_lds,
+    // spmv_xw_allow_lds)
+}
+
+int64_t device_values_f32_bytes(const DeviceMatrix *m)
+{
+    return m->values_f32 ? (int64_t) (m->n_values * sizeof(float)) : 0;
+}
+
+// seconds the narrowing kernel takes over the stream's values (a measurement for tools: the twin is rewritten
+// with what it already holds)
+double device_time_narrow_values(DeviceMatrix *m)
+{
+    if (!m->values_f32) throw FatalError("the matrix has no float copy of its values");
+    HIP_CHECK(hipSetDevice(m->device));
+    const size_t n_narrow = (m->n_values + 3) & ~(size_t) 3;
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipDeviceSynchronize());
+    launch_narrow_values(nullptr, m->values_f32, m->values, n_narrow);
+    HIP_CHECK(hipEventRecord(e0, nullptr));
+    launch_narrow_values(nullptr, m->values_f32, m->values, n_narrow);
+    HIP_CHECK(hipEventRecord(e1, nullptr));
+    HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    (void) hipEventDestroy(e0);
+    (void) hipEventDestroy(e1);
+    return 1e-3 * ms;
+}
+
+// y <- alpha*fl32(A)*x + beta*y: device_spmv through the kernels that read the float twin
+void device_spmv_f32(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_)
+{
+    if (!m->values_f32)
+        throw FatalError(m->symmetric ? "no float copy of the values: spx.gpu.values_f32 serves general matrices only, this one was tuned as a symmetric one"
+                                      : "no float copy of the values: the matrix was tuned or restored without spx.gpu.values_f32=true");
+    device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, nullptr, true);
 }
 
 // y <- alpha*A^T*x + beta*y.  A symmetric matrix is its own transpose: the forward product, with everything it
@@ -724,15 +803,23 @@ static KernelArgs kernel_args(const DeviceMatrix *m, double alpha, const double 
 
 // one launch over the row-blocks of `xcd_now`, through the kernel that the stream and the matrix' settings call
 // for; returns whether the spilled column sums still need csx_symfix_kernel
-static bool launch_rowblocks(const DeviceMatrix *m, const KernelArgs &a, const XcdSplit &xcd_now, uint32_t blocks,
-                             void *stream)
+// (`f32`, general streams with a float twin: the same family and wavefronts, the kernel that reads the twin)
+static bool launch_rowblocks(const DeviceMatrix *m, const KernelArgs &a_, const XcdSplit &xcd_now, uint32_t blocks,
+                             void *stream, bool f32 = false)
 {
     if (!blocks) return false;
+    if (f32 && (m->has_tiles || !m->values_f32)) throw FatalError("no float copy of the values");
+    KernelArgs af;
+    if (f32) {
+        af = a_;
+        af.values = reinterpret_cast<const double *>(m->values_f32);     // (StreamArgs::values of a float launch)
+    }
+    const KernelArgs &a = f32 ? af : a_;
     const size_t lds = m->lds_doubles * sizeof(double);
     if (m->wave_tiles && !m->accum) {
         // a copy of slots + y tile per wavefront: as many wavefronts as fit the LDS
         launch_spmv(m->has_tiles ? SpmvFamily::symtile_det : SpmvFamily::det, m->waves, blocks, (size_t) m->waves * lds,
-                    stream, a, xcd_now);
+                    stream, a, xcd_now, f32);
         return m->has_tiles && m->n_spill != 0;
     }
     if (m->has_tiles) {
@@ -757,15 +844,15 @@ static bool launch_rowblocks(const DeviceMatrix *m, const KernelArgs &a, const X
         return m->n_spill && !m->sym_atomic;
     }
     if (m->accum) {
-        launch_spmv(SpmvFamily::accum, m->waves, blocks, lds, stream, a, xcd_now);
+        launch_spmv(SpmvFamily::accum, m->waves, blocks, lds, stream, a, xcd_now, f32);
     } else if (m->xw_on && m->passes_xw) {
         KernelArgs ax = a;
         ax.passes = m->passes_xw;
         ax.descs = m->xdescs;
         ax.xw_tab = m->xw_tab;
-        launch_spmv_xw(m->waves, blocks, (size_t) m->lds_doubles_xw * sizeof(double), stream, ax, xcd_now);
+        launch_spmv_xw(m->waves, blocks, (size_t) m->lds_doubles_xw * sizeof(double), stream, ax, xcd_now, f32);
     } else {
-        launch_spmv(SpmvFamily::plain, m->waves, blocks, lds, stream, a, xcd_now);
+        launch_spmv(SpmvFamily::plain, m->waves, blocks, lds, stream, a, xcd_now, f32);
     }
     return false;
 }
@@ -845,7 +932,7 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
 // the stream and the matrix' settings call for (launch_rowblocks), K = 2, 4, 8 (device_mv_group: streams without
 // symmetric tiles or read-once segments, or with spx.gpu.sym_matmat) the K-vector kernels over the plain stream.
 static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
-                           size_t ldy, void *stream_, const SpmvPart *part)
+                           size_t ldy, void *stream_, const SpmvPart *part, bool f32)
 {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
@@ -901,7 +988,7 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
         if (ph > 0) a.beta = 1.0;
         const XcdSplit &split = part ? part->split : m->xcd_split[ph];
         const uint32_t blocks = 8u * (part ? part->longest : m->xcd_longest[ph]);
-        if (K == 1) need_symfix |= launch_rowblocks(m, a, split, blocks, stream_);
+        if (K == 1) need_symfix |= launch_rowblocks(m, a, split, blocks, stream_, f32);
         else launch_rowblocks_mv(m, K, a, ldx, ldy, split, blocks, stream_);
     }
     if (part && !part->last) {
@@ -1572,6 +1659,10 @@ void device_poke(DeviceMatrix *m, bool diagonal, size_t index, double value)
     quiesce_before_edit(m);
     HIP_CHECK(hipMemcpy((diagonal ? m->dvalues : m->values) + index, &value, sizeof(value),
                         hipMemcpyHostToDevice));
+    if (!diagonal && m->values_f32) {
+        const float narrow = (float) value;          // (round to nearest even, as the kernels narrow)
+        HIP_CHECK(hipMemcpy(m->values_f32 + index, &narrow, sizeof(narrow), hipMemcpyHostToDevice));
+    }
 }
 
 // ---- new values, same pattern ---------------------------------------------------------------------------
@@ -1637,7 +1728,7 @@ void device_set_values(DeviceMatrix *m, const double *d_csr_values, void *stream
                          ", the calling thread's current device is " + std::to_string(cur));
     if (!m->has_plan) throw FatalError("no values plan: call spx_hip_mat_values_plan first");
     m->launched_since_edit = true;
-    if (m->plan_values) launch_refresh_values(stream, m->values, m->plan_values, d_csr_values, m->n_values);
+    if (m->plan_values) launch_refresh_values(stream, m->values, m->plan_values, d_csr_values, m->n_values, m->values_f32);
     if (m->plan_mirror) launch_refresh_values(stream, m->mirror_val, m->plan_mirror, d_csr_values, m->n_mirror_nnz);
     if (m->plan_diag) launch_refresh_values(stream, m->dvalues + m->plan_diag_lo, m->plan_diag, d_csr_values, m->plan_n_diag);
 }

@@ -9,6 +9,12 @@
 // an absent cell of a tile) stores its other values one by one and leaves that position alone: it keeps the
 // bits the tune put there.  The plan is padded to a multiple of four entries (no source), so that the last
 // group needs no bounds of its own.
+//
+// A stream with a float twin of its values (spx.gpu.values_f32) gets both arrays written in the same pass: a
+// full group stores one float4 more, the others store the float next to every double they store and leave the
+// float bits of a position without a source alone as well.  The twin itself is built once per tune or restore
+// by csx_narrow_values_kernel from the doubles already in HBM: per lane four consecutive values, two 16-byte
+// loads, one 16-byte store; 12 B per value, no host pass.
 #include "spmv_launch.hpp"
 
 #include "hip_check.hpp"
@@ -24,10 +30,11 @@ constexpr unsigned REFRESH_BLOCK = 256;
 
 // n_quads groups of four positions; `dst` 16-byte aligned when ALIGNED (the diagonal array of a slice that
 // starts on an odd row is not: its groups store value by value)
-template <bool ALIGNED>
+// F32: dst32 is the float twin of dst (16-byte aligned like it), written next to it
+template <bool ALIGNED, bool F32 = false>
 __global__ void __launch_bounds__(REFRESH_BLOCK)
 csx_refresh_values_kernel(double *__restrict__ dst, const uint4 *__restrict__ map, const double *__restrict__ src,
-                          size_t n, size_t n_quads)
+                          size_t n, size_t n_quads, float *__restrict__ dst32 = nullptr)
 {
     const size_t q = (size_t) blockIdx.x * REFRESH_BLOCK + threadIdx.x;
     if (q >= n_quads) return;
@@ -40,17 +47,37 @@ csx_refresh_values_kernel(double *__restrict__ dst, const uint4 *__restrict__ ma
         double2 *out = reinterpret_cast<double2 *>(dst + i);
         out[0] = make_double2(a, b);
         out[1] = make_double2(c, d);
+        if (F32)
+            *reinterpret_cast<float4 *>(dst32 + i) =
+                make_float4(__double2float_rn(a), __double2float_rn(b), __double2float_rn(c), __double2float_rn(d));
         return;
     }
-    if (m.x != REFRESH_NONE && i < n) dst[i] = src[m.x];
-    if (m.y != REFRESH_NONE && i + 1 < n) dst[i + 1] = src[m.y];
-    if (m.z != REFRESH_NONE && i + 2 < n) dst[i + 2] = src[m.z];
-    if (m.w != REFRESH_NONE && i + 3 < n) dst[i + 3] = src[m.w];
+#define SPX_REFRESH_ONE(mk, k)                                                                   \
+    if (mk != REFRESH_NONE && i + k < n) {                                                       \
+        const double v = src[mk];                                                                \
+        dst[i + k] = v;                                                                          \
+        if (F32) dst32[i + k] = __double2float_rn(v);                                            \
+    }
+    SPX_REFRESH_ONE(m.x, 0)
+    SPX_REFRESH_ONE(m.y, 1)
+    SPX_REFRESH_ONE(m.z, 2)
+    SPX_REFRESH_ONE(m.w, 3)
+#undef SPX_REFRESH_ONE
+}
+
+// the float twin of a value array: n_quads groups of four, dst[i] = (float) src[i], round to nearest even
+__global__ void __launch_bounds__(REFRESH_BLOCK)
+csx_narrow_values_kernel(float4 *__restrict__ dst, const double2 *__restrict__ src, size_t n_quads)
+{
+    const size_t q = (size_t) blockIdx.x * REFRESH_BLOCK + threadIdx.x;
+    if (q >= n_quads) return;
+    const double2 a = src[2 * q], b = src[2 * q + 1];
+    dst[q] = make_float4(__double2float_rn(a.x), __double2float_rn(a.y), __double2float_rn(b.x), __double2float_rn(b.y));
 }
 
 }  // namespace
 
-void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n)
+void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n, float *dst_f32)
 {
     if (!n) return;
     const size_t n_quads = (n + 3) / 4;
@@ -58,10 +85,30 @@ void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const
     if (blocks > 0x7fffffffull) throw FatalError("value refresh: array too long for one launch");
     const uint4 *map4 = reinterpret_cast<const uint4 *>(map);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0)
-        hipLaunchKernelGGL(csx_refresh_values_kernel<true>, dim3((unsigned) blocks), dim3(REFRESH_BLOCK), 0, st, dst, map4, src, n, n_quads);
+    if (dst_f32) {
+        if (((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(dst_f32)) & 15u) != 0)
+            throw FatalError("value refresh: a value array with a float twin must be 16-byte aligned");
+        hipLaunchKernelGGL((csx_refresh_values_kernel<true, true>), dim3((unsigned) blocks), dim3(REFRESH_BLOCK), 0, st, dst, map4, src, n,
+                           n_quads, dst_f32);
+    } else if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0)
+        hipLaunchKernelGGL(csx_refresh_values_kernel<true>, dim3((unsigned) blocks), dim3(REFRESH_BLOCK), 0, st, dst, map4, src, n, n_quads,
+                           static_cast<float *>(nullptr));
     else
-        hipLaunchKernelGGL(csx_refresh_values_kernel<false>, dim3((unsigned) blocks), dim3(REFRESH_BLOCK), 0, st, dst, map4, src, n, n_quads);
+        hipLaunchKernelGGL(csx_refresh_values_kernel<false>, dim3((unsigned) blocks), dim3(REFRESH_BLOCK), 0, st, dst, map4, src, n, n_quads,
+                           static_cast<float *>(nullptr));
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_narrow_values(void *stream, float *dst, const double *src, size_t n)
+{
+    if (!n) return;
+    if ((n & 3u) || ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u))
+        throw FatalError("float twin of the values: arrays of a multiple of four elements, 16-byte aligned");
+    const size_t n_quads = n / 4;
+    const size_t blocks = (n_quads + REFRESH_BLOCK - 1) / REFRESH_BLOCK;
+    if (blocks > 0x7fffffffull) throw FatalError("float twin of the values: array too long for one launch");
+    hipLaunchKernelGGL(csx_narrow_values_kernel, dim3((unsigned) blocks), dim3(REFRESH_BLOCK), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<float4 *>(dst), reinterpret_cast<const double2 *>(src), n_quads);
     HIP_CHECK(hipGetLastError());
 }
 

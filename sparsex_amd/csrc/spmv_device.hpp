@@ -29,6 +29,16 @@ typedef double spx_d2u_t __attribute__((ext_vector_type(2), aligned(8)));
 __device__ __forceinline__ double2 ld_stream(const double2 *p) { return *p; }
 __device__ __forceinline__ double ld_stream(const double *p) { return *p; }
 __device__ __forceinline__ uint2 ld_stream(const uint2 *p) { return *p; }
+// (the float twin of the values, spx.gpu.values_f32: the same loads at half the width)
+typedef float spx_f2u_t __attribute__((ext_vector_type(2), aligned(4)));
+__device__ __forceinline__ float2 ld_stream(const float2 *p) { return *p; }
+__device__ __forceinline__ float ld_stream(const float *p) { return *p; }
+// The type of the stream's values, V: double, or float for the products that read the float twin
+// (csx_spmv_f32_kernel and its kin: StreamArgs::values then POINTS AT FLOATS, element for element the array
+// of doubles).  Values widen in registers; every product and sum is fp64 whatever V is.
+template <class V> struct ValueVec;
+template <> struct ValueVec<double> { typedef double2 pair; typedef spx_d2u_t pair_u; };
+template <> struct ValueVec<float> { typedef float2 pair; typedef spx_f2u_t pair_u; };
 #define SPX_LD_INDEX(expr) (expr)
 
 // set bits of `mask` in lanes 1..lane (bit 0 is never set by the emitter)
@@ -44,10 +54,10 @@ __device__ __forceinline__ uint32_t starts_upto(uint64_t mask, int lane)
 // row's leftover nonzeros, each with a column offset of its own (gather pass, G: SPX_PASS_GATHER 1,
 // SPX_PASS_GATHER_LDS 2).  The single-vector and the K-vector interpreter below are compositions of these.
 
-template <int W>
+template <int W, class V = double>
 struct PassValues {
-    double2 v2[W / 2 > 0 ? W / 2 : 1];
-    double v1;
+    typename ValueVec<V>::pair v2[W / 2 > 0 ? W / 2 : 1];
+    V v1;
 };
 
 // The index load of pass `ps` into q (uint2) and goff (uint32_t[G ? W : 1]).  G: the lane's row comes from the
@@ -95,16 +105,16 @@ struct PassValues {
         }                                                                                                              \
     } while (0)
 
-// the value load: interleaved pairs, 16 bytes per lane and load
-template <int W>
-__device__ __forceinline__ PassValues<W> load_values(const StreamArgs &a, const SpxRowBlock &rb, const SpxPass &ps, uint32_t l)
+// the value load: interleaved pairs, 16 bytes per lane and load (floats: 8)
+template <int W, class V = double>
+__device__ __forceinline__ PassValues<W, V> load_values(const StreamArgs &a, const SpxRowBlock &rb, const SpxPass &ps, uint32_t l)
 {
-    PassValues<W> v;
+    PassValues<W, V> v;
     const uint32_t nseg = ps.nseg;
-    const double *vals = a.values + rb.val_off + ps.val_off;
+    const V *vals = reinterpret_cast<const V *>(a.values) + rb.val_off + ps.val_off;
 #pragma unroll
     for (int p = 0; p < W / 2; ++p)
-        v.v2[p] = ld_stream(reinterpret_cast<const double2 *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
+        v.v2[p] = ld_stream(reinterpret_cast<const typename ValueVec<V>::pair *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
     if (W & 1) v.v1 = ld_stream(vals + (uint32_t) (W / 2) * 2u * nseg + l);
     return v;
 }
@@ -166,16 +176,16 @@ __device__ __forceinline__ void load_x(const double *xp, double (&x)[W])
 }
 
 // the lane's partial sum: W fused multiply-adds, in column order
-template <int W>
-__device__ __forceinline__ double dot(const PassValues<W> &v, const double (&x)[W])
+template <int W, class V>
+__device__ __forceinline__ double dot(const PassValues<W, V> &v, const double (&x)[W])
 {
     double t = 0.0;
 #pragma unroll
     for (int p = 0; p < W / 2; ++p) {
-        t = fma(v.v2[p].x, x[2 * p], t);
-        t = fma(v.v2[p].y, x[2 * p + 1], t);
+        t = fma((double) v.v2[p].x, x[2 * p], t);
+        t = fma((double) v.v2[p].y, x[2 * p + 1], t);
     }
-    if (W & 1) t = fma(v.v1, x[W - 1], t);
+    if (W & 1) t = fma((double) v.v1, x[W - 1], t);
     return t;
 }
 
@@ -194,7 +204,7 @@ __device__ __forceinline__ void wave_add(double *p, double t, int lane)
 
 // one vector.  (Row, x and dot product pass by pass: decoding all passes first and then applying them, the
 // K-vector order below, costs the single-vector kernels five to eight VGPRs: profiles/r08/REFACTOR.md.)
-template <int W, int B, int G, int K = 1>
+template <int W, int B, int G, int K = 1, class V = double>
 __device__ __forceinline__ void unit_passes(const KernelArgs &a, const SpxRowBlock &rb,
                                             const SpxPass (&ps)[B], double *tile,
                                             const double *win, int lane)
@@ -209,9 +219,9 @@ __device__ __forceinline__ void unit_passes(const KernelArgs &a, const SpxRowBlo
         l[b] = active[b] ? (uint32_t) lane : 0u;         // idle lanes shadow lane 0
         SPX_LOAD_INDEX(W, G, a, rb, ps[b], active[b], l[b], lane, q[b], goff[b]);
     }
-    PassValues<W> v[B];
+    PassValues<W, V> v[B];
 #pragma unroll
-    for (int b = 0; b < B; ++b) v[b] = load_values<W>(a, rb, ps[b], l[b]);
+    for (int b = 0; b < B; ++b) v[b] = load_values<W, V>(a, rb, ps[b], l[b]);
     int row[B];
     double acc[B];
 #pragma unroll
@@ -228,7 +238,7 @@ __device__ __forceinline__ void unit_passes(const KernelArgs &a, const SpxRowBlo
             row[b] = o.row;
             load_x(a.x + (q[b].x + (uint32_t) o.dcol), x);
         }
-        acc[b] = dot<W>(v[b], x);
+        acc[b] = dot<W, V>(v[b], x);
     }
     if (G == 1 && rb.n_rows == 1) {
         double t = 0.0;
@@ -245,8 +255,8 @@ __device__ __forceinline__ void unit_passes(const KernelArgs &a, const SpxRowBlo
 // K vectors (column-major: vector j of x at a.x + j * a.ldx): index and values once, then for every vector
 // its x, the dot products and the adds to ITS y tile (vector j at tile + j * n_rows).  `win`: the K staged x
 // windows (vector j at win + j * xwin_len) where MvArgs::stage says so, else the SPX_PASS_GATHER_LDS offsets
-// gather through L2 relative to xwin_base.
-template <int W, int B, int G, int K>
+// gather through L2 relative to xwin_base.  (V: so that run_units names both compositions alike; doubles only)
+template <int W, int B, int G, int K, class V = double>
 __device__ __forceinline__ void unit_passes(const MvArgs &a, const SpxRowBlock &rb, const SpxPass (&ps)[B],
                                             double *tile, const double *win, int lane)
 {
@@ -323,39 +333,39 @@ __device__ __forceinline__ void unit_passes(const MvArgs &a, const SpxRowBlock &
 }
 
 // B passes of one kind, by their width (wave-uniform)
-template <int B, int G, int K = 1, class Args>
+template <int B, int G, int K = 1, class V = double, class Args>
 __device__ __forceinline__ void run_units(const Args &a, const SpxRowBlock &rb,
                                           const SpxPass (&ps)[B], double *tile, const double *win,
                                           int lane)
 {
     switch (ps[0].width) {         // wave-uniform
-    case 1: unit_passes<1, B, G, K>(a, rb, ps, tile, win, lane); break;
-    case 2: unit_passes<2, B, G, K>(a, rb, ps, tile, win, lane); break;
-    case 3: unit_passes<3, B, G, K>(a, rb, ps, tile, win, lane); break;
-    case 4: unit_passes<4, B, G, K>(a, rb, ps, tile, win, lane); break;
-    case 5: unit_passes<5, 1, G, K>(a, rb, {ps[0]}, tile, win, lane);
-            if (B > 1) unit_passes<5, 1, G, K>(a, rb, {ps[B - 1]}, tile, win, lane);
+    case 1: unit_passes<1, B, G, K, V>(a, rb, ps, tile, win, lane); break;
+    case 2: unit_passes<2, B, G, K, V>(a, rb, ps, tile, win, lane); break;
+    case 3: unit_passes<3, B, G, K, V>(a, rb, ps, tile, win, lane); break;
+    case 4: unit_passes<4, B, G, K, V>(a, rb, ps, tile, win, lane); break;
+    case 5: unit_passes<5, 1, G, K, V>(a, rb, {ps[0]}, tile, win, lane);
+            if (B > 1) unit_passes<5, 1, G, K, V>(a, rb, {ps[B - 1]}, tile, win, lane);
             break;
-    case 6: unit_passes<6, 1, G, K>(a, rb, {ps[0]}, tile, win, lane);
-            if (B > 1) unit_passes<6, 1, G, K>(a, rb, {ps[B - 1]}, tile, win, lane);
+    case 6: unit_passes<6, 1, G, K, V>(a, rb, {ps[0]}, tile, win, lane);
+            if (B > 1) unit_passes<6, 1, G, K, V>(a, rb, {ps[B - 1]}, tile, win, lane);
             break;
-    case 7: unit_passes<7, 1, G, K>(a, rb, {ps[0]}, tile, win, lane);
-            if (B > 1) unit_passes<7, 1, G, K>(a, rb, {ps[B - 1]}, tile, win, lane);
+    case 7: unit_passes<7, 1, G, K, V>(a, rb, {ps[0]}, tile, win, lane);
+            if (B > 1) unit_passes<7, 1, G, K, V>(a, rb, {ps[B - 1]}, tile, win, lane);
             break;
-    default: unit_passes<8, 1, G, K>(a, rb, {ps[0]}, tile, win, lane);
-            if (B > 1) unit_passes<8, 1, G, K>(a, rb, {ps[B - 1]}, tile, win, lane);
+    default: unit_passes<8, 1, G, K, V>(a, rb, {ps[0]}, tile, win, lane);
+            if (B > 1) unit_passes<8, 1, G, K, V>(a, rb, {ps[B - 1]}, tile, win, lane);
             break;
     }
 }
 
 // one pass on its own
-template <int K = 1, class Args>
+template <int K = 1, class V = double, class Args>
 __device__ __forceinline__ void run_pass(const Args &a, const SpxRowBlock &rb,
                                          const SpxPass &ps, double *tile, const double *win, int lane)
 {
-    if (ps.kind == SPX_PASS_GATHER) run_units<1, 1, K>(a, rb, {ps}, tile, win, lane);
-    else if (ps.kind == SPX_PASS_GATHER_LDS) run_units<1, 2, K>(a, rb, {ps}, tile, win, lane);
-    else run_units<1, 0, K>(a, rb, {ps}, tile, win, lane);
+    if (ps.kind == SPX_PASS_GATHER) run_units<1, 1, K, V>(a, rb, {ps}, tile, win, lane);
+    else if (ps.kind == SPX_PASS_GATHER_LDS) run_units<1, 2, K, V>(a, rb, {ps}, tile, win, lane);
+    else run_units<1, 0, K, V>(a, rb, {ps}, tile, win, lane);
 }
 
 // a wavefront's round of two passes, side by side when they have the same shape (they mostly do: passes
@@ -364,13 +374,13 @@ __device__ __forceinline__ bool same_shape(const SpxPass &p0, const SpxPass &p1)
 {
     return p0.kind == p1.kind && p0.width == p1.width;
 }
-template <int K = 1, class Args>
+template <int K = 1, class V = double, class Args>
 __device__ __forceinline__ void run_pair(const Args &a, const SpxRowBlock &rb, const SpxPass (&ps)[2],
                                          double *tile, const double *win, int lane)
 {
-    if (ps[0].kind == SPX_PASS_GATHER) run_units<2, 1, K>(a, rb, ps, tile, win, lane);
-    else if (ps[0].kind == SPX_PASS_GATHER_LDS) run_units<2, 2, K>(a, rb, ps, tile, win, lane);
-    else run_units<2, 0, K>(a, rb, ps, tile, win, lane);
+    if (ps[0].kind == SPX_PASS_GATHER) run_units<2, 1, K, V>(a, rb, ps, tile, win, lane);
+    else if (ps[0].kind == SPX_PASS_GATHER_LDS) run_units<2, 2, K, V>(a, rb, ps, tile, win, lane);
+    else run_units<2, 0, K, V>(a, rb, ps, tile, win, lane);
 }
 
 // ---- pass headers as six dwords (the pipelined kernels: spmv_xw_kernels.hip, spmv_sx_kernels.hip) ----

@@ -18,6 +18,7 @@
 // csx_sym_spmv_tmpl.c:60-106): every stored nonzero a(r,c) contributes
 // alpha*a*x[c] to y[r]; on the symmetric path the stream also holds the mirror
 // image of every stored unit, so a(r,c) contributes alpha*a*x[r] to y[c] too.
+#include "hip_check.hpp"
 #include "spmv_device.hpp"
 #include "spmv_launch.hpp"
 #include "spmv_sym_device.hpp"
@@ -45,7 +46,12 @@ namespace spx {
 // own, and the copies are summed in wavefront order before the write-out -- the
 // only thing in this library whose order of additions is not fixed is the LDS adds
 // of different wavefronts of a workgroup into the shared tile.
-template <bool SYM, bool ATOMIC, int WAVES_PER_BLOCK, bool DET = false, bool SEGS = false, bool TILES = true>
+//
+// V (general forms only): the type of the values the passes load -- double, or float for the products on the
+// float twin of the value array (spx.gpu.values_f32; a.values then points at floats).  Same loads at half the
+// width, same element offsets, widened in registers: the FMAs, the tile and the write-out are fp64 either way.
+template <bool SYM, bool ATOMIC, int WAVES_PER_BLOCK, bool DET = false, bool SEGS = false, bool TILES = true,
+          class V = double>
 __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &xs,
                                           double *lds)
 {
@@ -106,29 +112,29 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
             } else {
                 if (p0.kind == SPX_PASS_SYMSEG) run_symseg(a, rb, p0, mine, tile, lane);
                 else if (TILES && p0.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p0, mine, tile, lane);
-                else run_pass(a, rb, p0, tile, win, lane);
+                else run_pass<1, V>(a, rb, p0, tile, win, lane);
                 if (two) {
                     if (p1.kind == SPX_PASS_SYMSEG) run_symseg(a, rb, p1, mine, tile, lane);
                     else if (TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
-                    else run_pass(a, rb, p1, tile, win, lane);
+                    else run_pass<1, V>(a, rb, p1, tile, win, lane);
                 }
             }
         } else if (SYM && TILES && p0.kind == SPX_PASS_SYMTILE) {
             symtile_pass(a, rb, p0, mine, tile, lane);
             if (two) {
                 if (p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
-                else run_pass(a, rb, p1, tile, win, lane);
+                else run_pass<1, V>(a, rb, p1, tile, win, lane);
             }
         } else if (two) {
             if (same_shape(p0, p1)) {
-                run_pair(a, rb, {p0, p1}, tile, win, lane);
+                run_pair<1, V>(a, rb, {p0, p1}, tile, win, lane);
             } else {
-                run_pass(a, rb, p0, tile, win, lane);
+                run_pass<1, V>(a, rb, p0, tile, win, lane);
                 if (SYM && TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
-                else run_pass(a, rb, p1, tile, win, lane);
+                else run_pass<1, V>(a, rb, p1, tile, win, lane);
             }
         } else {
-            run_pass(a, rb, p0, tile, win, lane);
+            run_pass<1, V>(a, rb, p0, tile, win, lane);
         }
         if (t + 2 * WAVES_PER_BLOCK < n_pass) {
             p0 = passes[t + 2 * WAVES_PER_BLOCK];
@@ -249,6 +255,34 @@ void csx_spmv_det_kernel(SPX_KERNEL_PARAMS)
     SPX_KERNEL_ARGS(a);
     extern __shared__ double lds_dyn[];      // a y tile per wavefront, then the x window
     spmv_body<false, false, WAVES, true>(a, xcd_split, lds_dyn);
+}
+
+// ---- the general forms on the float twin of the values (spx_hip_matvec_kernel_f32) ----------------------
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<false, false, WAVES, false, false, true, float>(a, xcd_split, lds_dyn);
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_accum_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<false, true, WAVES, false, false, true, float>(a, xcd_split, lds_dyn);
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_det_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<false, false, WAVES, true, false, true, float>(a, xcd_split, lds_dyn);
 }
 
 template <int WAVES>
@@ -380,11 +414,26 @@ static SpmvKernel spmv_kernel(SpmvFamily family)
     return csx_spmv_kernel<WAVES>;
 }
 
+// the float twin's kernel of a general family (the symmetric families have none: nullptr)
+template <int WAVES>
+static SpmvKernel spmv_f32_kernel(SpmvFamily family)
+{
+    switch (family) {
+    case SpmvFamily::plain: return csx_spmv_f32_kernel<WAVES>;
+    case SpmvFamily::accum: return csx_spmv_accum_f32_kernel<WAVES>;
+    case SpmvFamily::det: return csx_spmv_det_f32_kernel<WAVES>;
+    default: break;
+    }
+    return nullptr;
+}
+
 void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a,
-                 const XcdSplit &xs)
+                 const XcdSplit &xs, bool f32)
 {
     const int w = (waves == 2 || waves == 8) ? waves : 4;
-    const SpmvKernel k = w == 2 ? spmv_kernel<2>(family) : w == 8 ? spmv_kernel<8>(family) : spmv_kernel<4>(family);
+    const SpmvKernel k = f32 ? (w == 2 ? spmv_f32_kernel<2>(family) : w == 8 ? spmv_f32_kernel<8>(family) : spmv_f32_kernel<4>(family))
+                             : (w == 2 ? spmv_kernel<2>(family) : w == 8 ? spmv_kernel<8>(family) : spmv_kernel<4>(family));
+    if (!k) throw FatalError("no float-value kernel for this family of streams");
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * w), lds_bytes, static_cast<hipStream_t>(stream), a.rbs, a.passes,
                        a.n_rb, a.pass_stride, xs, a.values, a.descs, a.cidx, a.segrows, a.x, a.y, a.carry, a.dvalues,
                        a.spill, a.slot_col, a.alpha, a.beta, a.dvalues_priv, a.beta_priv);
@@ -395,6 +444,8 @@ void spmv_allow_lds(SpmvFamily family, size_t bytes)
     const int b = (int) bytes;
     for (SpmvKernel k : {spmv_kernel<2>(family), spmv_kernel<4>(family), spmv_kernel<8>(family)})
         (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    for (SpmvKernel k : {spmv_f32_kernel<2>(family), spmv_f32_kernel<4>(family), spmv_f32_kernel<8>(family)})
+        if (k) (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b);
 }
 
 void launch_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,

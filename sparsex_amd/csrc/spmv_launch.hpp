@@ -67,8 +67,10 @@ enum class SpmvFamily {
 };
 
 // spmv_kernels.hip (`waves`: 2, 4 or 8, anything else runs as 4; `stream`: a hipStream_t)
+// `f32` (plain, accum and det only; launch_spmv_xw as well): the kernel that reads the float twin of the values
+// (spx.gpu.values_f32) -- a.values then points at that array of floats, element for element the doubles'
 void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a,
-                 const XcdSplit &xs);
+                 const XcdSplit &xs, bool f32 = false);
 void spmv_allow_lds(SpmvFamily family, size_t bytes);      // dynamic LDS beyond the default 64 KB
 // the steps around the row-block launches, for `nvec` vectors at once (gridDim.y; vector j of x at x + j * ldx,
 // of y at y + j * ldy, its carry slots at carry + j * n_carry)
@@ -91,7 +93,8 @@ size_t spmv_sx_header_bytes(uint32_t pass_stride);
 void spmv_sx_allow_lds(size_t bytes);
 
 // spmv_xw_kernels.hip
-void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs);
+void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs,
+                    bool f32 = false);
 void spmv_xw_allow_lds(size_t bytes);
 
 // spmv_t_kernels.hip: the transposed product of a general stream, y += alpha * A^T * x (every launch adds: the
@@ -145,6 +148,11 @@ void spmv_mvsym_allow_lds(size_t bytes);
 // refresh_kernels.hip: dst[i] = src[map[i]] for the n positions of a value array of the stream, where map[i] is
 // not 0xffffffff (values_plan.hpp).  `map` holds n rounded up to a multiple of four entries, the padding without a
 // source.  Enqueues on `stream`, nothing else.
-void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n);
+// `dst_f32` (or null): the float twin of dst, which gets the same values rounded to nearest in the same pass
+// (both 16-byte aligned then).
+void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n,
+                           float *dst_f32 = nullptr);
+// dst[i] = (float) src[i] for i < n, round to nearest even; n a multiple of four, both arrays 16-byte aligned
+void launch_narrow_values(void *stream, float *dst, const double *src, size_t n);
 
 }  // namespace spx

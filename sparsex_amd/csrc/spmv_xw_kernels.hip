@@ -40,22 +40,24 @@ namespace spx {
 // (W = 1: {v0, -}; 2: {v0, v1}; 3: {v0, v1}, {v2, -}; 4: {v0, v1}, {v2, v3}; "-" is whatever follows in
 // the value array, never used).  The same number of loads for every pass is what lets passes of
 // different widths follow each other in one pipeline, and lets the compiler count its loads.
-template <int B>
+// V: the type of the values, double or float (the float twin of the value array, spx.gpu.values_f32: a.values
+// then points at floats).  Floats come as two 2-float loads at 4-byte granularity, at the same element offsets.
+template <int B, class V = double>
 struct XwStage {
     uint2 q[B];                // {offset of segment 0 in the unit windows, descriptor bits}
     uint32_t segl[B];          // segments of the row-block in front of the lane's | lane active << 16
     uint32_t width[B];         // (wave-uniform)
     uint32_t row0[B];          // (wave-uniform) first row of the pass' part of the row-block (SpxPass::elem0)
-    spx_d2u_t va[B], vb[B];
+    typename ValueVec<V>::pair_u va[B], vb[B];
 };
 
 // The loads of a stage.  Everything the second half needs of the headers goes into the stage with them:
 // the headers are dead once their loads are out.  (The descriptor comes from the descriptor array also
 // where the header holds a copy: x comes from LDS once the values are there, so the copy would save no
 // round trip here.)
-template <int B>
+template <int B, class V = double>
 __device__ __forceinline__ void xw_issue(const KernelArgs &a, const SpxRowBlock &rb, const PassWords (&ps)[B],
-                                         XwStage<B> &S, int lane)
+                                         XwStage<B, V> &S, int lane)
 {
 #pragma unroll
     for (int b = 0; b < B; ++b) {
@@ -68,31 +70,31 @@ __device__ __forceinline__ void xw_issue(const KernelArgs &a, const SpxRowBlock 
         const uint64_t mk = (ps[b].flags() & SPX_PASSF_INLINE) ? 0ull : ps[b].mask();
         const uint32_t rank = ps[b].rank0() + (active ? starts_upto(mk, lane) : 0u);
         S.q[b] = ld_stream(reinterpret_cast<const uint2 *>(a.descs + rb.desc_off + rank));
-        const double *vals = a.values + rb.val_off + ps[b].val_off();
+        const V *vals = reinterpret_cast<const V *>(a.values) + rb.val_off + ps[b].val_off();
         const uint32_t off_a = W == 1u ? l : 2u * l;
         const uint32_t off_b = W == 3u ? 2u * nseg + l : (W == 4u ? 2u * nseg + 2u * l : off_a);
-        S.va[b] = *reinterpret_cast<const spx_d2u_t *>(vals + off_a);
-        S.vb[b] = *reinterpret_cast<const spx_d2u_t *>(vals + off_b);
+        S.va[b] = *reinterpret_cast<const typename ValueVec<V>::pair_u *>(vals + off_a);
+        S.vb[b] = *reinterpret_cast<const typename ValueVec<V>::pair_u *>(vals + off_b);
     }
 }
 
 // ... and what follows once they have arrived: rows and window offsets, x from LDS, W FMAs, one LDS add
-template <int W>
-__device__ __forceinline__ void xw_finish_pass(uint2 q, uint32_t segl, uint32_t row0, spx_d2u_t va, spx_d2u_t vb,
+template <int W, class V2 = spx_d2u_t>
+__device__ __forceinline__ void xw_finish_pass(uint2 q, uint32_t segl, uint32_t row0, V2 va, V2 vb,
                                                double *tile, const double *xw)
 {
     const UnitOrigin o = unit_origin(q.y, segl, row0);
     const int row = o.row;
     const double *xp = xw + (int) (q.x + (uint32_t) o.dcol);         // (q.x: an offset into the unit windows)
-    double t = va.x * xp[0];
-    if (W >= 2) t = fma(va.y, xp[1], t);
-    if (W >= 3) t = fma(vb.x, xp[2], t);
-    if (W >= 4) t = fma(vb.y, xp[3], t);
+    double t = (double) va.x * xp[0];
+    if (W >= 2) t = fma((double) va.y, xp[1], t);
+    if (W >= 3) t = fma((double) vb.x, xp[2], t);
+    if (W >= 4) t = fma((double) vb.y, xp[3], t);
     if (segl >> 16) atomicAdd(&tile[row], t);
 }
 
-template <int B>
-__device__ __forceinline__ void xw_finish(const XwStage<B> &S, double *tile, const double *xw)
+template <int B, class V = double>
+__device__ __forceinline__ void xw_finish(const XwStage<B, V> &S, double *tile, const double *xw)
 {
 #pragma unroll
     for (int b = 0; b < B; ++b) {
@@ -106,7 +108,7 @@ __device__ __forceinline__ void xw_finish(const XwStage<B> &S, double *tile, con
 }
 
 // a unit pass of width 5..8 that reads LDS, on its own (not pipelined)
-template <int W>
+template <int W, class V = double>
 __device__ __forceinline__ void xw_wide(const KernelArgs &a, const SpxRowBlock &rb, const PassWords &ps,
                                         double *tile, const double *xw, int lane)
 {
@@ -116,12 +118,12 @@ __device__ __forceinline__ void xw_wide(const KernelArgs &a, const SpxRowBlock &
     const uint64_t mk = (ps.flags() & SPX_PASSF_INLINE) ? 0ull : ps.mask();
     const uint32_t rank = ps.rank0() + (active ? starts_upto(mk, lane) : 0u);
     const uint2 q = ld_stream(reinterpret_cast<const uint2 *>(a.descs + rb.desc_off + rank));
-    const double *vals = a.values + rb.val_off + ps.val_off();
-    double2 v2[W / 2];
-    double v1 = 0.0;
+    const V *vals = reinterpret_cast<const V *>(a.values) + rb.val_off + ps.val_off();
+    typename ValueVec<V>::pair v2[W / 2];
+    V v1 = 0;
 #pragma unroll
     for (int p = 0; p < W / 2; ++p)
-        v2[p] = ld_stream(reinterpret_cast<const double2 *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
+        v2[p] = ld_stream(reinterpret_cast<const typename ValueVec<V>::pair *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
     if (W & 1) v1 = ld_stream(vals + (uint32_t) (W / 2) * 2u * nseg + l);
     const UnitOrigin o = unit_origin(q.y, ps.seg0() + l, ps.w[5]);
     const int row = o.row;
@@ -129,32 +131,33 @@ __device__ __forceinline__ void xw_wide(const KernelArgs &a, const SpxRowBlock &
     double t = 0.0;
 #pragma unroll
     for (int p = 0; p < W / 2; ++p) {
-        t = fma(v2[p].x, xp[2 * p], t);
-        t = fma(v2[p].y, xp[2 * p + 1], t);
+        t = fma((double) v2[p].x, xp[2 * p], t);
+        t = fma((double) v2[p].y, xp[2 * p + 1], t);
     }
-    if (W & 1) t = fma(v1, xp[W - 1], t);
+    if (W & 1) t = fma((double) v1, xp[W - 1], t);
     if (active) atomicAdd(&tile[row], t);
 }
 
 // one pass of any kind on its own
+template <class V = double>
 __device__ __forceinline__ void xw_one(const KernelArgs &a, const SpxRowBlock &rb, const PassWords &ps,
                                        double *tile, const double *win, const double *xw, int lane)
 {
     if (ps.kind() == SPX_PASS_UNIT && (ps.flags() & SPX_PASSF_XLDS)) {
         if (ps.width() <= 4u) {
-            XwStage<1> S;
-            xw_issue<1>(a, rb, {ps}, S, lane);
-            xw_finish<1>(S, tile, xw);
+            XwStage<1, V> S;
+            xw_issue<1, V>(a, rb, {ps}, S, lane);
+            xw_finish<1, V>(S, tile, xw);
             return;
         }
         switch (ps.width()) {            // wave-uniform
-        case 5: xw_wide<5>(a, rb, ps, tile, xw, lane); break;
-        case 6: xw_wide<6>(a, rb, ps, tile, xw, lane); break;
-        case 7: xw_wide<7>(a, rb, ps, tile, xw, lane); break;
-        default: xw_wide<8>(a, rb, ps, tile, xw, lane); break;
+        case 5: xw_wide<5, V>(a, rb, ps, tile, xw, lane); break;
+        case 6: xw_wide<6, V>(a, rb, ps, tile, xw, lane); break;
+        case 7: xw_wide<7, V>(a, rb, ps, tile, xw, lane); break;
+        default: xw_wide<8, V>(a, rb, ps, tile, xw, lane); break;
         }
     } else {
-        run_pass(a, rb, ps.pass(), tile, win, lane);
+        run_pass<1, V>(a, rb, ps.pass(), tile, win, lane);
     }
 }
 
@@ -176,11 +179,11 @@ __device__ __forceinline__ int xw_in_range(int t, int lo, int hi)
 // undid the pipeline.  Deeper pipelines were measured -- three and four rounds in flight, with empty rounds
 // at the ends so that no load sits under a branch: slower on the five rounds a wavefront has per row-block,
 // and what they gain in flight they lose in wavefronts per SIMD: profiles/r05/ablation.md.)
-template <int WAVES>
+template <int WAVES, class V = double>
 __device__ __forceinline__ void xw_run(const KernelArgs &a, const SpxRowBlock &rb, const uint32_t *hdr, int hi,
-                                       int n_in, int &t, XwStage<2> &A, double *tile, const double *xw, int lane)
+                                       int n_in, int &t, XwStage<2, V> &A, double *tile, const double *xw, int lane)
 {
-    XwStage<2> B;
+    XwStage<2, V> B;
     PassWords c0, c1;
     const int n_rounds = (n_in + 1) / 2, t_end = t + n_in * WAVES;
     // (headers of the next round: read from LDS while the current round's second half runs)
@@ -194,25 +197,25 @@ __device__ __forceinline__ void xw_run(const KernelArgs &a, const SpxRowBlock &r
     int r = 1;
     for (; r + 1 < n_rounds; r += 2) {
         SPX_XW_HEADERS();
-        xw_issue<2>(a, rb, {c0, c1}, B, lane);
-        xw_finish<2>(A, tile, xw);
+        xw_issue<2, V>(a, rb, {c0, c1}, B, lane);
+        xw_finish<2, V>(A, tile, xw);
         SPX_XW_HEADERS();
-        xw_issue<2>(a, rb, {c0, c1}, A, lane);
-        xw_finish<2>(B, tile, xw);
+        xw_issue<2, V>(a, rb, {c0, c1}, A, lane);
+        xw_finish<2, V>(B, tile, xw);
     }
     if (r < n_rounds) {
         SPX_XW_HEADERS();
-        xw_issue<2>(a, rb, {c0, c1}, B, lane);
-        xw_finish<2>(A, tile, xw);
-        xw_finish<2>(B, tile, xw);
+        xw_issue<2, V>(a, rb, {c0, c1}, B, lane);
+        xw_finish<2, V>(A, tile, xw);
+        xw_finish<2, V>(B, tile, xw);
     } else {
-        xw_finish<2>(A, tile, xw);
+        xw_finish<2, V>(A, tile, xw);
     }
     t = t_end;
 #undef SPX_XW_HEADERS
 }
 
-template <int WAVES>
+template <int WAVES, class V = double>
 __device__ __forceinline__ void spmv_body_xw(const KernelArgs &a, const XcdSplit &xs, double *lds)
 {
     constexpr int BLOCK_THREADS = 64 * WAVES;
@@ -282,26 +285,26 @@ __device__ __forceinline__ void spmv_body_xw(const KernelArgs &a, const XcdSplit
     const int n_pass = rb.n_pass;
     int t = wave;
     const int n_first = xw_in_range<WAVES>(t, lo, hi);
-    XwStage<2> A;
+    XwStage<2, V> A;
     if (n_first > 0) {
         if (t + WAVES >= hi) c1 = no_pass(c0);
-        xw_issue<2>(a, rb, {c0, c1}, A, lane);
+        xw_issue<2, V>(a, rb, {c0, c1}, A, lane);
     }
     __syncthreads();
 
-    if (n_first > 0) xw_run<WAVES>(a, rb, hdr, hi, n_first, t, A, tile, xw, lane);
+    if (n_first > 0) xw_run<WAVES, V>(a, rb, hdr, hi, n_first, t, A, tile, xw, lane);
     while (t < n_pass) {
         const int n_in = xw_in_range<WAVES>(t, lo, hi);
         c0 = lds_pass(hdr, t);
         c1 = lds_pass(hdr, t + WAVES);
         if (n_in > 0) {
             if (t + WAVES >= hi) c1 = no_pass(c0);
-            xw_issue<2>(a, rb, {c0, c1}, A, lane);
-            xw_run<WAVES>(a, rb, hdr, hi, n_in, t, A, tile, xw, lane);
+            xw_issue<2, V>(a, rb, {c0, c1}, A, lane);
+            xw_run<WAVES, V>(a, rb, hdr, hi, n_in, t, A, tile, xw, lane);
             continue;
         }
-        xw_one(a, rb, c0, tile, win, xw, lane);
-        if (t + WAVES < n_pass) xw_one(a, rb, c1, tile, win, xw, lane);
+        xw_one<V>(a, rb, c0, tile, win, xw, lane);
+        if (t + WAVES < n_pass) xw_one<V>(a, rb, c1, tile, win, xw, lane);
         t += 2 * WAVES;
     }
     __syncthreads();
@@ -328,17 +331,35 @@ void csx_spmv_xw_kernel(SPX_KERNEL_PARAMS, const XwEntry *xw_tab_)
     spmv_body_xw<WAVES>(a, xcd_split, lds_dyn);
 }
 
-void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream_, const KernelArgs &a, const XcdSplit &xs)
+// ... on the float twin of the values (spx_hip_matvec_kernel_f32)
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_xw_f32_kernel(SPX_KERNEL_PARAMS, const XwEntry *xw_tab_)
+{
+    SPX_KERNEL_ARGS(a);
+    a.xw_tab = xw_tab_;
+    extern __shared__ double lds_dyn[];
+    spmv_body_xw<WAVES, float>(a, xcd_split, lds_dyn);
+}
+
+void launch_spmv_xw(int waves, unsigned blocks, size_t lds_bytes, void *stream_, const KernelArgs &a, const XcdSplit &xs,
+                    bool f32)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define SPX_LAUNCH_XW(W)                                                                           \
-    hipLaunchKernelGGL(csx_spmv_xw_kernel<W>, dim3(blocks), dim3(64 * W), lds_bytes, stream, a.rbs,  \
+#define SPX_LAUNCH_XW(KERNEL, W)                                                                   \
+    hipLaunchKernelGGL(KERNEL<W>, dim3(blocks), dim3(64 * W), lds_bytes, stream, a.rbs,              \
                        a.passes, a.n_rb, a.pass_stride, xs, a.values, a.descs, a.cidx, a.segrows,   \
                        a.x, a.y, a.carry, a.dvalues, a.spill, a.slot_col, a.alpha, a.beta,           \
                        a.dvalues_priv, a.beta_priv, a.xw_tab)
-    if (waves == 2) SPX_LAUNCH_XW(2);
-    else if (waves == 8) SPX_LAUNCH_XW(8);
-    else SPX_LAUNCH_XW(4);
+    if (f32) {
+        if (waves == 2) SPX_LAUNCH_XW(csx_spmv_xw_f32_kernel, 2);
+        else if (waves == 8) SPX_LAUNCH_XW(csx_spmv_xw_f32_kernel, 8);
+        else SPX_LAUNCH_XW(csx_spmv_xw_f32_kernel, 4);
+    } else {
+        if (waves == 2) SPX_LAUNCH_XW(csx_spmv_xw_kernel, 2);
+        else if (waves == 8) SPX_LAUNCH_XW(csx_spmv_xw_kernel, 8);
+        else SPX_LAUNCH_XW(csx_spmv_xw_kernel, 4);
+    }
 #undef SPX_LAUNCH_XW
 }
 
@@ -349,6 +370,9 @@ void spmv_xw_allow_lds(size_t bytes)
     (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_xw_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, b);
     (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_xw_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, b);
     (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_xw_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_xw_f32_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_xw_f32_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+    (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_xw_f32_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, b);
 }
 
 }  // namespace spx

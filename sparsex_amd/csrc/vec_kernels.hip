@@ -583,6 +583,18 @@ spx_error_t spx_hip_matvec_kernel_vec(spx_value_t alpha, const spx_matrix_t *A,
     return spx_hip_matvec_kernel(alpha, A, x->data, beta, y->data, stream);
 }
 
+spx_error_t spx_hip_matvec_kernel_f32_vec(spx_value_t alpha, const spx_matrix_t *A,
+                                          const spx_hip_vec_t *x, spx_value_t beta,
+                                          spx_hip_vec_t *y, void *stream)
+{
+    if (!x || !y) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid device vector"); return SPX_FAILURE; }
+    if (A && (x->size != (size_t) spx_mat_get_ncols(A) || y->size != (size_t) spx_mat_get_nrows(A))) {
+        SETERROR_0(SPX_ERR_DIM);
+        return SPX_FAILURE;
+    }
+    return spx_hip_matvec_kernel_f32(alpha, A, x->data, beta, y->data, stream);
+}
+
 spx_error_t spx_hip_matvec_trans_kernel_vec(spx_value_t alpha, const spx_matrix_t *A,
                                             const spx_hip_vec_t *x, spx_value_t beta,
                                             spx_hip_vec_t *y, void *stream)
