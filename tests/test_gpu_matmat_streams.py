@@ -79,7 +79,9 @@ def test_symmetric_random_matmat_mirrored(seed):
 
 @pytest.mark.parametrize("seed", range(40, 90))
 def test_symmetric_random_matmat_any_path(seed):
-    """random_sym_options: tiles and read-once segments run one product per column (group 1)."""
+    """random_sym_options: tiles and read-once segments run one product per column (group 1) unless the tune opts
+    in with spx.gpu.sym_matmat=true: test_gpu_random_paths.py runs these seeds through that path
+    (csx_spmv_mvsym_kernel)."""
     import torch
     _random_case(torch, seed, True, random_sym_options(seed, random_options(seed)), False)
 
