@@ -106,11 +106,14 @@
  *                           the window plan stages fewer doubles than it serves nonzeros) | "true" | "false" -- unit passes
  *                           accumulate in the row-block's unit windows in LDS, which are added to y once, instead of one
  *                           atomic add per nonzero; read by spx_mat_tune / spx_mat_restore, not saved with the matrix
- *   spx.gpu.values_f32      "false" (default) | "true": a general tune keeps a float copy of the stream's values in HBM
- *                           next to the doubles (half of value_bytes, an allocation of its own, also with
+ *   spx.gpu.values_f32      "false" (default) | "true" | "all".  "true": a general tune keeps a float copy of the stream's
+ *                           values in HBM next to the doubles (half of value_bytes, an allocation of its own, also with
  *                           spx.gpu.arena), built on the device once the launch tuner has settled, for
- *                           spx_hip_matvec_kernel_f32; symmetric tunes ignore it; any other value fails the tune;
- *                           read by spx_mat_tune / spx_mat_restore, not saved with the matrix
+ *                           spx_hip_matvec_kernel_f32; symmetric tunes ignore it.  "all": general tunes as under "true",
+ *                           and symmetric tunes keep the copy of their stream's values too (the stored triangle, read
+ *                           once as floats; the diagonal and a slice's thin mirror list get no copy and are rounded in
+ *                           registers).  Any other value fails the tune; read by spx_mat_tune / spx_mat_restore, not
+ *                           saved with the matrix
  *   spx.vec.device          "false" (default) | "true" (also: env SPX_VEC_DEVICE through spx_options_set_from_env):
  *                           vectors the library allocates itself (spx_vec_create, spx_vec_create_random; page-locked)
  *                           keep x's HBM copy between spx_matvec_* calls, reused while no spx_vec_* call has changed
@@ -214,8 +217,8 @@ int spx_hip_matvec_trans_mode(const spx_matrix_t *A);
  * (nearest even).  For solvers that multiply with a rounded matrix most of the time (the correction step of
  * iterative refinement, an inner or preconditioning Krylov solve) and with the exact one for the residual: both
  * products run on ONE handle -- the same pattern, tune, descriptor stream and launch configuration; the float copy
- * of the values (spx.gpu.values_f32=true at spx_mat_tune / spx_mat_restore, general matrices only) costs half of
- * value_bytes of HBM and halves the value bytes a product reads.  Vectors stay fp64, every product and sum is
+ * of the values (spx.gpu.values_f32=true at spx_mat_tune / spx_mat_restore for general matrices, =all for symmetric
+ * ones as well) costs half of value_bytes of HBM and halves the value bytes a product reads.  Vectors stay fp64, every product and sum is
  * fp64: the kernels load floats, widen them in registers and run the fp64 kernels' operations in their order.
  * Semantics are those of spx_hip_matvec_kernel in every respect (rows written by a slice or an attached matrix,
  * beta == 0 never reads y_dev, enqueues only, allocates nothing, hipGraph-capturable, the handle's single-stream
@@ -224,15 +227,24 @@ int spx_hip_matvec_trans_mode(const spx_matrix_t *A);
  * fp64 product runs.  Accuracy: within the fp64 bound of the exact product with fl32(A), hence within
  * 2^-24 * |alpha| * sum|a||x| plus that bound of the product with A.  Stored values beyond float's range become
  * +-inf in the copy, values below its normal range become subnormal or 0.
+ * A symmetric handle (spx.gpu.values_f32=all): fl32(A) rounds EVERY stored entry -- the lower triangle of the
+ * stream, mirror-image copies the stream stores (spx.gpu.sym_once=false), the diagonal, the thin mirror list of a
+ * slice.  Only the stream's value array has a copy (4 bytes per value, as for general streams); the diagonal and
+ * the mirror list, at most a value per row, are read as doubles and rounded in registers by the float product
+ * alone.  Every read-once family has its float form (tiles with lists or atomics, read-once segments with and
+ * without tiles, the pipelined kernel, the deterministic one): with the atomic hand-over the result lies within
+ * the bound above and is not bit-reproducible, like the fp64 product's.
  * spx_hip_mat_set_values(_host) writes both arrays in the same pass, spx_mat_set_entry patches the float next
  * to the double; spx_mat_get_entry, spx_mat_save, export and every other product read the doubles, as without
  * the option.
  * SPX_FAILURE (through the error handler, nothing enqueued) for a NULL handle or pointer, overlapping x and y
  * ranges, the wrong current device, a host-only matrix, (_vec) vectors whose sizes are not ncols / nrows, and a
- * matrix WITHOUT a float copy -- tuned or restored without the option, or tuned as a symmetric one; the message
- * says which.  There is no silent fp64 fallback.
- * Not provided: float forms of the multi-vector, transposed, parts and dist products, host vectors, symmetric
- * streams.
+ * matrix WITHOUT a float copy -- tuned or restored without the option, or tuned as a symmetric one without
+ * spx.gpu.values_f32=all; the message says which.  There is no silent fp64 fallback.
+ * Not provided: float forms of the multi-vector products (the one on read-once symmetric streams,
+ * spx.gpu.sym_matmat, included), of the transposed, parts and dist products (spx_hip_matvec_trans_* on a symmetric
+ * handle keeps running the fp64 forward product), host vectors, and a launch tune of their own for the float
+ * kernels (they run with the wavefronts and the family measured for the fp64 product).
  */
 spx_error_t spx_hip_matvec_mult_f32(spx_value_t alpha, const spx_matrix_t *A, const spx_value_t *x_dev,
                                     spx_value_t *y_dev, void *stream);

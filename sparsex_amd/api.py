@@ -331,19 +331,22 @@ class Matrix:
 
     def hip_matvec_kernel_f32(self, alpha, x_ptr, beta, y_ptr, stream=0):
         """``spx_hip_matvec_kernel_f32``: y <- alpha*fl32(A)*x + beta*y on HBM pointers, with the float copy of
-        the values (spx.gpu.values_f32=true at tune or restore time); vectors, products and sums are fp64."""
+        the values (spx.gpu.values_f32=true at tune or restore time; a symmetric tune keeps one with =all, and
+        its float product rounds the diagonal and the thin mirror list in registers); vectors, products and sums
+        are fp64."""
         rc = lib().spx_hip_matvec_kernel_f32(alpha, self.handle, x_ptr, beta, y_ptr, stream)
         if rc != SPX_SUCCESS:
             raise SpxError("spx_hip_matvec_kernel_f32 failed (see stderr)")
 
     def values_f32_bytes(self):
-        """``spx_hip_mat_values_f32_bytes``: bytes of HBM the float copy of the values takes, 0 without one,
-        -1 for a matrix without a device copy."""
+        """``spx_hip_mat_values_f32_bytes``: bytes of HBM the float copy of the values takes (4 per value of the
+        stream, general or symmetric), 0 without one, -1 for a matrix without a device copy."""
         return int(lib().spx_hip_mat_values_f32_bytes(self.handle))
 
     def matvec_f32(self, alpha, x, beta, y, stream=None):
         """y <- alpha*fl32(A)*x + beta*y for 1-D contiguous torch float64 tensors on the matrix' device: x of ncols
-        elements, y of nrows.  `stream`: a torch stream (default: the current one of y's device).  Returns y."""
+        elements, y of nrows.  `stream`: a torch stream (default: the current one of y's device).  Returns y.
+        General handles tuned with spx.gpu.values_f32=true or all, symmetric ones tuned with all."""
         import torch
         pairs = (("x", x, self.ncols), ("y", y, self.nrows))
         for name, t, n in pairs:
@@ -753,7 +756,8 @@ def matvec_kernel_vec(A, alpha, x, beta, y, stream=0):
 
 
 def matvec_kernel_f32_vec(A, alpha, x, beta, y, stream=0):
-    """``spx_hip_matvec_kernel_f32_vec``: y <- alpha*fl32(A)*x + beta*y on DeviceVectors (x: ncols, y: nrows)."""
+    """``spx_hip_matvec_kernel_f32_vec``: y <- alpha*fl32(A)*x + beta*y on DeviceVectors (x: ncols, y: nrows);
+    general handles tuned with spx.gpu.values_f32=true or all, symmetric ones with all."""
     rc = lib().spx_hip_matvec_kernel_f32_vec(alpha, A.handle, x.handle, beta, y.handle, stream)
     if rc != SPX_SUCCESS:
         raise SpxError("spx_hip_matvec_kernel_f32_vec failed (see stderr)")

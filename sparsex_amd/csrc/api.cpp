@@ -964,17 +964,20 @@ static int read_trans_windows()
     return tw == "auto" ? -1 : (tw == "true" ? 1 : 0);
 }
 
-// spx.gpu.values_f32: a float copy of a general stream's values for spx_hip_matvec_kernel_f32.  Read where the
-// device copy is built, like spx.gpu.trans_windows; not saved with the matrix.
-static bool read_values_f32()
+// spx.gpu.values_f32: a float copy of a stream's values for spx_hip_matvec_kernel_f32 -- 0 false, 1 true (general
+// tunes; symmetric ones ignore it), 2 all (symmetric tunes too).  Read where the device copy is built, like
+// spx.gpu.trans_windows; not saved with the matrix.
+static int read_values_f32()
 {
     const std::string v = Config::instance().get_str("spx.gpu.values_f32");
-    if (v != "true" && v != "false") {
-        log_msg(LOG_ERR, "spx.gpu.values_f32: true or false\n");
+    if (v != "true" && v != "false" && v != "all") {
+        log_msg(LOG_ERR, "spx.gpu.values_f32: false, true or all\n");
         throw FatalError("bad spx.gpu.values_f32");
     }
-    return v == "true";
+    return v == "all" ? 2 : (v == "true" ? 1 : 0);
 }
+// whether a tune or restore that read `mode` keeps the copy
+static bool wants_values_f32(int mode, bool symmetric) { return mode == 2 || (mode == 1 && !symmetric); }
 
 static spx_matrix_t *do_tune(spx_input_t *in)
 {
@@ -1291,8 +1294,8 @@ static spx_matrix_t *do_tune(spx_input_t *in)
     }
 
     // the float copy of the values, once, of the stream the tuners settled on (none of their trial uploads
-    // pays for it); symmetric tunes ignore the option
-    if (A->dev && A->values_f32 && !sym) device_build_values_f32(A->dev);
+    // pays for it); symmetric tunes ignore "true" and keep one with "all"
+    if (A->dev && wants_values_f32(A->values_f32, sym)) device_build_values_f32(A->dev);
 
     if (!cfg.get_bool("spx.rt.keep_encoded")) {
         std::vector<Partition> *old = new std::vector<Partition>();
@@ -1947,7 +1950,7 @@ try {
             A->dev = device_upload(*gs, (size_t) A->nrows, (size_t) A->ncols, A->symmetric != 0,
                                    A->own_lo, A->own_hi, A->device_ordinal);
             device_set_trans_windows(A->dev, A->trans_windows);
-            if (A->values_f32 && !A->symmetric) device_build_values_f32(A->dev);
+            if (wants_values_f32(A->values_f32, A->symmetric != 0)) device_build_values_f32(A->dev);
             keep_index(A.get(), std::move(*gs));
         } else {
             A->host_stream = std::move(gs);

@@ -74,7 +74,7 @@ void Config::reset_defaults()
     props_["spx.gpu.unit_windows"] = "auto";   // general path: the columns of a row-block's unit passes staged in LDS, unit passes pipelined: true | false | auto (measured)
     props_["spx.gpu.unit_window_doubles"] = "3072";  // ... most doubles of x a row-block may stage for them
     props_["spx.gpu.unit_window_gap"] = "16";  // ... column intervals closer than this are staged as one
-    props_["spx.gpu.values_f32"] = "false";    // general tunes: a float copy of the stream's values next to the doubles, for spx_hip_matvec_kernel_f32: true | false; read at tune / restore time, not saved
+    props_["spx.gpu.values_f32"] = "false";    // a float copy of the stream's values next to the doubles, for spx_hip_matvec_kernel_f32: false | true (general tunes) | all (symmetric tunes too); read at tune / restore time, not saved
     props_["spx.gpu.trans_windows"] = "auto";  // transposed product of a general matrix: unit passes accumulate in those windows in LDS: true | false | auto (where the plan stages fewer doubles than it serves nonzeros); read at tune / restore time, not saved
 }
 

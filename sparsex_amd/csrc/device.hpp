@@ -28,7 +28,9 @@ void device_free(DeviceMatrix *m);
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream);
 
-// The float twin of the stream's values (spx.gpu.values_f32; general streams only): device_build_values_f32
+// The float twin of the stream's values (spx.gpu.values_f32: general streams, and symmetric ones where the caller
+// read "all" -- the twin of `values` only, the diagonal and the thin mirror list are rounded by the float product
+// in registers): device_build_values_f32
 // allocates it (an allocation of its own, also with spx.gpu.arena) and fills it from the doubles in HBM with
 // csx_narrow_values_kernel -- synchronous, once per tune or restore, after the launch tuner has settled;
 // FatalError naming the size where HBM has no room.  device_values_f32_bytes: 4 bytes per stream value, 0 without

@@ -159,7 +159,8 @@ struct DeviceMatrix {
     uint32_t *plan_values = nullptr, *plan_mirror = nullptr, *plan_diag = nullptr;
     size_t plan_n_diag = 0, plan_diag_lo = 0, plan_csr_nnz = 0, plan_bytes = 0;
     bool has_plan = false;
-    // the float twin of `values` (spx.gpu.values_f32, general streams; device_build_values_f32): element i is
+    // the float twin of `values` (spx.gpu.values_f32: general streams, with "all" symmetric ones too;
+    // device_build_values_f32): element i is
     // values[i] rounded to nearest, tail slack included; an allocation of its own, also next to an arena
     float *values_f32 = nullptr;
 };
@@ -664,10 +665,12 @@ void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
 
 // ---- the float twin of the values ------------------------------------------------------------------------
 // Built from the doubles already in HBM (csx_narrow_values_kernel), once per tune or restore -- the caller
-// decides when: the trial uploads of a tune do not pay for it.  General streams only; synchronous.
+// decides when: the trial uploads of a tune do not pay for it.  Synchronous.  A symmetric stream (the caller asks
+// for it where spx.gpu.values_f32=all) gets the twin of its `values` like a general one -- the stored triangle and
+// whatever mirror-image copies the stream holds; its diagonal and thin mirror list have none (the float product
+// rounds them in registers).
 void device_build_values_f32(DeviceMatrix *m)
 {
-    if (m->symmetric) throw FatalError("float twin of the values: general streams only");
     HIP_CHECK(hipSetDevice(m->device));
     if (m->values_f32) {
         (void) hipFree(m->values_f32);
@@ -729,8 +732,8 @@ double device_time_narrow_values(DeviceMatrix *m)
 void device_spmv_f32(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_)
 {
     if (!m->values_f32)
-        throw FatalError(m->symmetric ? "no float copy of the values: spx.gpu.values_f32 serves general matrices only, this one was tuned as a symmetric one"
-                                      : "no float copy of the values: the matrix was tuned or restored without spx.gpu.values_f32=true");
+        throw FatalError(m->symmetric ? "no float copy of the values: this matrix was tuned as a symmetric one, and tuned or restored without spx.gpu.values_f32=all"
+                                      : "no float copy of the values: the matrix was tuned or restored without spx.gpu.values_f32=true (or all)");
     device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, nullptr, true);
 }
 
@@ -803,12 +806,12 @@ static KernelArgs kernel_args(const DeviceMatrix *m, double alpha, const double 
 
 // one launch over the row-blocks of `xcd_now`, through the kernel that the stream and the matrix' settings call
 // for; returns whether the spilled column sums still need csx_symfix_kernel
-// (`f32`, general streams with a float twin: the same family and wavefronts, the kernel that reads the twin)
+// (`f32`, streams with a float twin: the same family and wavefronts, the kernel that reads the twin)
 static bool launch_rowblocks(const DeviceMatrix *m, const KernelArgs &a_, const XcdSplit &xcd_now, uint32_t blocks,
                              void *stream, bool f32 = false)
 {
     if (!blocks) return false;
-    if (f32 && (m->has_tiles || !m->values_f32)) throw FatalError("no float copy of the values");
+    if (f32 && !m->values_f32) throw FatalError("no float copy of the values");
     KernelArgs af;
     if (f32) {
         af = a_;
@@ -829,17 +832,17 @@ static bool launch_rowblocks(const DeviceMatrix *m, const KernelArgs &a_, const 
         if (m->sym_atomic && m->has_symsegs && !m->has_symtiles && m->sx_on && m->passes_sx) {
             KernelArgs as = a;
             as.passes = m->passes_sx;
-            launch_spmv_sx(m->waves, blocks, lds_a + spmv_sx_header_bytes(m->pass_stride), stream, as, xcd_now, m->sx_tab);
+            launch_spmv_sx(m->waves, blocks, lds_a + spmv_sx_header_bytes(m->pass_stride), stream, as, xcd_now, m->sx_tab, f32);
         } else if (m->sym_atomic && m->has_symsegs && !m->has_symtiles) {
             // (16 wavefronts per workgroup, so that 2048-row row-blocks keep the SIMDs full, were
             // measured: 0.90 ms against 0.835 with 8, syn-nlpkkt; not built)
-            launch_spmv(SpmvFamily::symseg_notile, m->waves, blocks, lds_a, stream, a, xcd_now);
+            launch_spmv(SpmvFamily::symseg_notile, m->waves, blocks, lds_a, stream, a, xcd_now, f32);
         } else if (m->sym_atomic && m->has_symsegs) {
-            launch_spmv(SpmvFamily::symseg, m->waves, blocks, lds_a, stream, a, xcd_now);
+            launch_spmv(SpmvFamily::symseg, m->waves, blocks, lds_a, stream, a, xcd_now, f32);
         } else if (m->sym_atomic) {
-            launch_spmv(SpmvFamily::symtile_atomic, m->waves, blocks, lds_a, stream, a, xcd_now);
+            launch_spmv(SpmvFamily::symtile_atomic, m->waves, blocks, lds_a, stream, a, xcd_now, f32);
         } else {
-            launch_spmv(SpmvFamily::symtile, m->waves, blocks, lds, stream, a, xcd_now);
+            launch_spmv(SpmvFamily::symtile, m->waves, blocks, lds, stream, a, xcd_now, f32);
         }
         return m->n_spill && !m->sym_atomic;
     }
@@ -952,7 +955,7 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
         const size_t first = m->init_limited ? m->init_lo : 0, last = m->init_limited ? m->own_hi : m->nrows;
         auto init_rows = [&](size_t lo, size_t hi) {
             if (hi > lo && !abl::sym_no_init && (!part || part->first))
-                launch_sym_init(stream_, K, Y, ldy, X, ldx, m->dvalues, lo, hi, m->own_lo, m->own_hi, alpha, beta);
+                launch_sym_init(stream_, K, Y, ldy, X, ldx, m->dvalues, lo, hi, m->own_lo, m->own_hi, alpha, beta, f32);
         };
         if (K == 1 && m->sym_atomic && !m->wave_tiles && m->use_private && !abl::sym_no_private) {
             // (row-blocks that nobody else adds to store their rows themselves: SPX_RB_PRIVATE)
@@ -973,7 +976,7 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
         // sums) is added afterwards
         if (m->n_mirror_rows && (!part || part->first))
             launch_sym_mirror_rows(stream_, K, m->mirror_rows, m->mirror_ptr, m->mirror_col, m->mirror_val, X, ldx, Y, ldy,
-                                   alpha, m->n_mirror_rows);
+                                   alpha, m->n_mirror_rows, f32);
         a.beta = beta = 1.0;
     }
     if (m->accum && !m->symmetric) {
@@ -997,7 +1000,7 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
     }
     if (m->n_shared)
         launch_fixup(stream_, K, m->shared, m->n_shared, K == 1 ? m->carry : m->carry_mv, mv_n_carry(m), Y, ldy, alpha,
-                     beta, a.dvalues, X, ldx);
+                     beta, a.dvalues, X, ldx, f32);
     // the spilled column sums are added last: a row that is split over several row-blocks gets its
     // value (beta*y, the diagonal term, its partial sums) from the fix-up kernel above, by a store
     if (need_symfix) launch_symfix(stream_, m->fix_ptr, m->fix_idx, m->spill, Y, alpha, m->nrows);

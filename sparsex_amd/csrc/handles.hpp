@@ -107,7 +107,7 @@ struct matrix {
     int wave_tiles = -1;        // per-wavefront y tiles: 1 / 0, -1 = measured at tune time (spx.gpu.wave_tiles)
     int unit_windows = -1;      // spx.gpu.unit_windows: 1 / 0, -1 = measured at tune time
     bool xw_on = false;         // ... the product runs with the unit windows of x in LDS (csx_spmv_xw_kernel)
-    bool values_f32 = false;    // spx.gpu.values_f32 as read at tune / restore time (general tunes: a float copy of the values)
+    int values_f32 = 0;         // spx.gpu.values_f32 as read at tune / restore time: 0 false, 1 true (general tunes keep a float copy of the values), 2 all (symmetric tunes too)
     int trans_windows = -1;     // spx.gpu.trans_windows as read at tune / restore time: 1 / 0, -1 = auto (by atomic bytes)
     bool rb_joined = false;     // general path: row-blocks joined side by side (the launch tuner's choice for streams far beyond the Infinity Cache)
     int sym_pipeline = -1;      // spx.gpu.sym_pipeline: 1 / 0, -1 = measured at tune time

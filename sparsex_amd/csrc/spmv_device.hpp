@@ -39,6 +39,10 @@ __device__ __forceinline__ float ld_stream(const float *p) { return *p; }
 template <class V> struct ValueVec;
 template <> struct ValueVec<double> { typedef double2 pair; typedef spx_d2u_t pair_u; };
 template <> struct ValueVec<float> { typedef float2 pair; typedef spx_f2u_t pair_u; };
+// a value that has no twin (the diagonal and the thin mirror list of a symmetric stream: at most one per row), as
+// the product with values of type V sees it: rounded to V in registers, to nearest even
+template <class V>
+__device__ __forceinline__ double stored_as(double d) { return (double) (V) d; }
 #define SPX_LD_INDEX(expr) (expr)
 
 // set bits of `mask` in lanes 1..lane (bit 0 is never set by the emitter)

@@ -47,9 +47,11 @@ namespace spx {
 // only thing in this library whose order of additions is not fixed is the LDS adds
 // of different wavefronts of a workgroup into the shared tile.
 //
-// V (general forms only): the type of the values the passes load -- double, or float for the products on the
+// V: the type of the values the passes load -- double, or float for the products on the
 // float twin of the value array (spx.gpu.values_f32; a.values then points at floats).  Same loads at half the
 // width, same element offsets, widened in registers: the FMAs, the tile and the write-out are fp64 either way.
+// The diagonal of a symmetric stream has no twin: the float forms read its doubles and round them in registers
+// (stored_as<V>), so that the product is that of the matrix whose EVERY stored entry is rounded to float.
 template <bool SYM, bool ATOMIC, int WAVES_PER_BLOCK, bool DET = false, bool SEGS = false, bool TILES = true,
           class V = double>
 __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &xs,
@@ -101,28 +103,28 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
     const int n_pass = rb.n_pass;
     int t = wave;
     // (symmetric tiles: the tile passes at the head of the wavefront's list, one round trip each)
-    if (SYM && TILES && !abl::sym_no_tile_run) symtile_run<WAVES_PER_BLOCK>(a, rb, passes, n_pass, t, p0, p1, mine, tile, lane);
+    if (SYM && TILES && !abl::sym_no_tile_run) symtile_run<WAVES_PER_BLOCK, V>(a, rb, passes, n_pass, t, p0, p1, mine, tile, lane);
     for (; t < n_pass; t += 2 * WAVES_PER_BLOCK) {
         const bool two = t + WAVES_PER_BLOCK < n_pass;
         if (SEGS && (p0.kind == SPX_PASS_SYMSEG || (two && p1.kind == SPX_PASS_SYMSEG))) {
             // read-once row segments (atomic hand-over only); whatever shares the round runs on its own
             if (two && p0.kind == SPX_PASS_SYMSEG && p1.kind == SPX_PASS_SYMSEG &&
-                run_symseg2(a, rb, p0, p1, mine, tile, lane)) {
+                run_symseg2<V>(a, rb, p0, p1, mine, tile, lane)) {
                 // (both done)
             } else {
-                if (p0.kind == SPX_PASS_SYMSEG) run_symseg(a, rb, p0, mine, tile, lane);
-                else if (TILES && p0.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p0, mine, tile, lane);
+                if (p0.kind == SPX_PASS_SYMSEG) run_symseg<V>(a, rb, p0, mine, tile, lane);
+                else if (TILES && p0.kind == SPX_PASS_SYMTILE) symtile_pass<V>(a, rb, p0, mine, tile, lane);
                 else run_pass<1, V>(a, rb, p0, tile, win, lane);
                 if (two) {
-                    if (p1.kind == SPX_PASS_SYMSEG) run_symseg(a, rb, p1, mine, tile, lane);
-                    else if (TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
+                    if (p1.kind == SPX_PASS_SYMSEG) run_symseg<V>(a, rb, p1, mine, tile, lane);
+                    else if (TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass<V>(a, rb, p1, mine, tile, lane);
                     else run_pass<1, V>(a, rb, p1, tile, win, lane);
                 }
             }
         } else if (SYM && TILES && p0.kind == SPX_PASS_SYMTILE) {
-            symtile_pass(a, rb, p0, mine, tile, lane);
+            symtile_pass<V>(a, rb, p0, mine, tile, lane);
             if (two) {
-                if (p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
+                if (p1.kind == SPX_PASS_SYMTILE) symtile_pass<V>(a, rb, p1, mine, tile, lane);
                 else run_pass<1, V>(a, rb, p1, tile, win, lane);
             }
         } else if (two) {
@@ -130,7 +132,7 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
                 run_pair<1, V>(a, rb, {p0, p1}, tile, win, lane);
             } else {
                 run_pass<1, V>(a, rb, p0, tile, win, lane);
-                if (SYM && TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass(a, rb, p1, mine, tile, lane);
+                if (SYM && TILES && p1.kind == SPX_PASS_SYMTILE) symtile_pass<V>(a, rb, p1, mine, tile, lane);
                 else run_pass<1, V>(a, rb, p1, tile, win, lane);
             }
         } else {
@@ -165,7 +167,7 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
             // term and beta * y; the init pass leaves them out
             for (int i = threadIdx.x; i < n_rows; i += BLOCK_THREADS) {
                 const size_t g = (size_t) rb.row0 + i;
-                double t = a.alpha * (tile[i] + a.dvalues_priv[g] * a.x[g]);
+                double t = a.alpha * (tile[i] + stored_as<V>(a.dvalues_priv[g]) * a.x[g]);
                 if (a.beta_priv != 0.0) t += a.beta_priv * a.y[g];
                 a.y[g] = t;
             }
@@ -180,7 +182,7 @@ __device__ __forceinline__ void spmv_body(const KernelArgs &a, const XcdSplit &x
         for (int i = threadIdx.x; i < n_rows; i += BLOCK_THREADS) {
             const size_t g = (size_t) rb.row0 + i;
             double t = tile[i];
-            if (a.dvalues) t += a.dvalues[g] * a.x[g];
+            if (a.dvalues) t += stored_as<V>(a.dvalues[g]) * a.x[g];
             t *= a.alpha;
             if (a.beta != 0.0) t += a.beta * a.y[g];
             a.y[g] = t;
@@ -285,6 +287,52 @@ void csx_spmv_det_f32_kernel(SPX_KERNEL_PARAMS)
     spmv_body<false, false, WAVES, true, false, true, float>(a, xcd_split, lds_dyn);
 }
 
+// ---- ... and the symmetric forms: the stored triangle read once as floats, the diagonal rounded at the write-out
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_symtile_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<true, false, WAVES, false, false, true, float>(a, xcd_split, lds_dyn);
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_symtile_atomic_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<true, true, WAVES, false, false, true, float>(a, xcd_split, lds_dyn);
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_symseg_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<true, true, WAVES, false, true, true, float>(a, xcd_split, lds_dyn);
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_symseg_notile_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<true, true, WAVES, false, true, false, float>(a, xcd_split, lds_dyn);
+}
+
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_symtile_det_f32_kernel(SPX_KERNEL_PARAMS)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body<true, false, WAVES, true, false, true, float>(a, xcd_split, lds_dyn);
+}
+
 template <int WAVES>
 __global__ __launch_bounds__(64 * WAVES)
 void csx_spmv_symtile_det_kernel(SPX_KERNEL_PARAMS)
@@ -339,9 +387,12 @@ void csx_symfix_kernel(const uint32_t *fix_ptr, const uint32_t *fix_idx,
 // of x at x + j * ldx, of y at y + j * ldy) ------------------------------------------------------------------
 
 // rows split over several row-blocks: sum their partials (vector j's at carry + j * n_carry)
-__global__ void csx_fixup_kernel(const SpxSharedRow *shared, uint32_t n_shared, const double *carry, uint32_t n_carry,
-                                 double *y, size_t ldy, double alpha, double beta, const double *dvalues,
-                                 const double *x, size_t ldx)
+// (V, here and in the two steps of the symmetric path below: double, or float for the product on the float twin
+// of the values -- the diagonal and the thin mirror list have no twin and are rounded in registers, stored_as<V>)
+template <class V>
+__device__ __forceinline__ void fixup_body(const SpxSharedRow *shared, uint32_t n_shared, const double *carry, uint32_t n_carry,
+                                           double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                                           const double *x, size_t ldx)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_shared) return;
@@ -349,9 +400,21 @@ __global__ void csx_fixup_kernel(const SpxSharedRow *shared, uint32_t n_shared, 
     const SpxSharedRow sr = shared[i];
     const double *cj = carry + j * n_carry;
     double *yj = y + j * ldy;
-    double s = dvalues ? dvalues[sr.row] * x[j * ldx + sr.row] : 0.0;
+    double s = dvalues ? stored_as<V>(dvalues[sr.row]) * x[j * ldx + sr.row] : 0.0;
     for (uint32_t k = 0; k < sr.n_slots; ++k) s += cj[sr.first_slot + k];
     yj[sr.row] = (beta == 0.0) ? alpha * s : alpha * s + beta * yj[sr.row];
+}
+__global__ void csx_fixup_kernel(const SpxSharedRow *shared, uint32_t n_shared, const double *carry, uint32_t n_carry,
+                                 double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                                 const double *x, size_t ldx)
+{
+    fixup_body<double>(shared, n_shared, carry, n_carry, y, ldy, alpha, beta, dvalues, x, ldx);
+}
+__global__ void csx_fixup_f32_kernel(const SpxSharedRow *shared, uint32_t n_shared, const double *carry, uint32_t n_carry,
+                                     double *y, size_t ldy, double alpha, double beta, const double *dvalues,
+                                     const double *x, size_t ldx)
+{
+    fixup_body<float>(shared, n_shared, carry, n_carry, y, ldy, alpha, beta, dvalues, x, ldx);
 }
 
 // column slices in one launch, first step: y <- beta * y on the rows [lo, hi)
@@ -365,33 +428,57 @@ __global__ void csx_scale_kernel(double *y, size_t ldy, size_t lo, size_t hi, do
 // symmetric path, first step: y <- beta*y + alpha*diag(A)*x on the owned
 // rows, 0 elsewhere (the main kernel then accumulates; on several GPUs the
 // per-GPU vectors are summed afterwards)
-__global__ void csx_sym_init_kernel(double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
-                                    size_t first, size_t nrows, size_t own_lo, size_t own_hi, double alpha, double beta)
+template <class V>
+__device__ __forceinline__ void sym_init_body(double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
+                                              size_t first, size_t nrows, size_t own_lo, size_t own_hi, double alpha, double beta)
 {
     const size_t i = first + (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nrows) return;
     double *yj = y + (size_t) blockIdx.y * ldy;
     double v = 0.0;
     if (i >= own_lo && i < own_hi) {
-        v = alpha * dvalues[i] * x[(size_t) blockIdx.y * ldx + i];
+        v = alpha * stored_as<V>(dvalues[i]) * x[(size_t) blockIdx.y * ldx + i];
         if (beta != 0.0) v += beta * yj[i];
     }
     yj[i] = v;
+}
+__global__ void csx_sym_init_kernel(double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
+                                    size_t first, size_t nrows, size_t own_lo, size_t own_hi, double alpha, double beta)
+{
+    sym_init_body<double>(y, ldy, x, ldx, dvalues, first, nrows, own_lo, own_hi, alpha, beta);
+}
+__global__ void csx_sym_init_f32_kernel(double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
+                                        size_t first, size_t nrows, size_t own_lo, size_t own_hi, double alpha, double beta)
+{
+    sym_init_body<float>(y, ldy, x, ldx, dvalues, first, nrows, own_lo, own_hi, alpha, beta);
 }
 
 // symmetric slice: the thinly spread part of the mirror image on rows of other
 // processes (GpuStream::mirror_*): one thread per such row, its few nonzeros in
 // fixed order.  The rows are distinct and no row-block touches them.
-__global__ void csx_sym_mirror_rows_kernel(const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
-                                           const double *val, const double *x, size_t ldx, double *y, size_t ldy,
-                                           double alpha, uint32_t n)
+template <class V>
+__device__ __forceinline__ void sym_mirror_rows_body(const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                                                     const double *val, const double *x, size_t ldx, double *y, size_t ldy,
+                                                     double alpha, uint32_t n)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     const double *xj = x + (size_t) blockIdx.y * ldx;
     double s = 0.0;
-    for (uint32_t k = ptr[t]; k < ptr[t + 1]; ++k) s = fma(val[k], xj[col[k]], s);
+    for (uint32_t k = ptr[t]; k < ptr[t + 1]; ++k) s = fma(stored_as<V>(val[k]), xj[col[k]], s);
     y[(size_t) blockIdx.y * ldy + rows[t]] = alpha * s;          // (nothing else adds to these rows: no need to clear them first)
+}
+__global__ void csx_sym_mirror_rows_kernel(const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                                           const double *val, const double *x, size_t ldx, double *y, size_t ldy,
+                                           double alpha, uint32_t n)
+{
+    sym_mirror_rows_body<double>(rows, ptr, col, val, x, ldx, y, ldy, alpha, n);
+}
+__global__ void csx_sym_mirror_rows_f32_kernel(const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
+                                               const double *val, const double *x, size_t ldx, double *y, size_t ldy,
+                                               double alpha, uint32_t n)
+{
+    sym_mirror_rows_body<float>(rows, ptr, col, val, x, ldx, y, ldy, alpha, n);
 }
 
 // ---- launchers ------------------------------------------------------------------------------
@@ -414,17 +501,21 @@ static SpmvKernel spmv_kernel(SpmvFamily family)
     return csx_spmv_kernel<WAVES>;
 }
 
-// the float twin's kernel of a general family (the symmetric families have none: nullptr)
+// the float twin's kernel of a family
 template <int WAVES>
 static SpmvKernel spmv_f32_kernel(SpmvFamily family)
 {
     switch (family) {
-    case SpmvFamily::plain: return csx_spmv_f32_kernel<WAVES>;
     case SpmvFamily::accum: return csx_spmv_accum_f32_kernel<WAVES>;
+    case SpmvFamily::symtile: return csx_spmv_symtile_f32_kernel<WAVES>;
+    case SpmvFamily::symtile_atomic: return csx_spmv_symtile_atomic_f32_kernel<WAVES>;
+    case SpmvFamily::symseg: return csx_spmv_symseg_f32_kernel<WAVES>;
+    case SpmvFamily::symseg_notile: return csx_spmv_symseg_notile_f32_kernel<WAVES>;
     case SpmvFamily::det: return csx_spmv_det_f32_kernel<WAVES>;
-    default: break;
+    case SpmvFamily::symtile_det: return csx_spmv_symtile_det_f32_kernel<WAVES>;
+    case SpmvFamily::plain: break;
     }
-    return nullptr;
+    return csx_spmv_f32_kernel<WAVES>;
 }
 
 void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a,
@@ -433,7 +524,6 @@ void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes
     const int w = (waves == 2 || waves == 8) ? waves : 4;
     const SpmvKernel k = f32 ? (w == 2 ? spmv_f32_kernel<2>(family) : w == 8 ? spmv_f32_kernel<8>(family) : spmv_f32_kernel<4>(family))
                              : (w == 2 ? spmv_kernel<2>(family) : w == 8 ? spmv_kernel<8>(family) : spmv_kernel<4>(family));
-    if (!k) throw FatalError("no float-value kernel for this family of streams");
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * w), lds_bytes, static_cast<hipStream_t>(stream), a.rbs, a.passes,
                        a.n_rb, a.pass_stride, xs, a.values, a.descs, a.cidx, a.segrows, a.x, a.y, a.carry, a.dvalues,
                        a.spill, a.slot_col, a.alpha, a.beta, a.dvalues_priv, a.beta_priv);
@@ -445,22 +535,22 @@ void spmv_allow_lds(SpmvFamily family, size_t bytes)
     for (SpmvKernel k : {spmv_kernel<2>(family), spmv_kernel<4>(family), spmv_kernel<8>(family)})
         (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b);
     for (SpmvKernel k : {spmv_f32_kernel<2>(family), spmv_f32_kernel<4>(family), spmv_f32_kernel<8>(family)})
-        if (k) (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b);
+        (void) hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b);
 }
 
 void launch_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
-                     size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha, double beta)
+                     size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha, double beta, bool f32)
 {
     const int t = 256;
-    hipLaunchKernelGGL(csx_sym_init_kernel, dim3((unsigned)((hi - lo + t - 1) / t), (unsigned) nvec), dim3(t), 0,
+    hipLaunchKernelGGL(f32 ? csx_sym_init_f32_kernel : csx_sym_init_kernel, dim3((unsigned)((hi - lo + t - 1) / t), (unsigned) nvec), dim3(t), 0,
                        static_cast<hipStream_t>(stream), y, ldy, x, ldx, dvalues, lo, hi, own_lo, own_hi, alpha, beta);
 }
 
 void launch_sym_mirror_rows(void *stream, int nvec, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
                             const double *val, const double *x, size_t ldx, double *y, size_t ldy, double alpha,
-                            uint32_t n)
+                            uint32_t n, bool f32)
 {
-    hipLaunchKernelGGL(csx_sym_mirror_rows_kernel, dim3((n + 255) / 256, (unsigned) nvec), dim3(256), 0,
+    hipLaunchKernelGGL(f32 ? csx_sym_mirror_rows_f32_kernel : csx_sym_mirror_rows_kernel, dim3((n + 255) / 256, (unsigned) nvec), dim3(256), 0,
                        static_cast<hipStream_t>(stream), rows, ptr, col, val, x, ldx, y, ldy, alpha, n);
 }
 
@@ -473,9 +563,9 @@ void launch_scale(void *stream, int nvec, double *y, size_t ldy, size_t lo, size
 
 void launch_fixup(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
                   uint32_t n_carry, double *y, size_t ldy, double alpha, double beta, const double *dvalues,
-                  const double *x, size_t ldx)
+                  const double *x, size_t ldx, bool f32)
 {
-    hipLaunchKernelGGL(csx_fixup_kernel, dim3((n_shared + 63) / 64, (unsigned) nvec), dim3(64), 0,
+    hipLaunchKernelGGL(f32 ? csx_fixup_f32_kernel : csx_fixup_kernel, dim3((n_shared + 63) / 64, (unsigned) nvec), dim3(64), 0,
                        static_cast<hipStream_t>(stream), shared, n_shared, carry, n_carry, y, ldy, alpha, beta, dvalues,
                        x, ldx);
 }

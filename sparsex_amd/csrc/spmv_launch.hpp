@@ -67,28 +67,30 @@ enum class SpmvFamily {
 };
 
 // spmv_kernels.hip (`waves`: 2, 4 or 8, anything else runs as 4; `stream`: a hipStream_t)
-// `f32` (plain, accum and det only; launch_spmv_xw as well): the kernel that reads the float twin of the values
-// (spx.gpu.values_f32) -- a.values then points at that array of floats, element for element the doubles'
+// `f32` (every family; launch_spmv_sx and launch_spmv_xw as well): the kernel that reads the float twin of the values
+// (spx.gpu.values_f32) -- a.values then points at that array of floats, element for element the doubles'.  The
+// steps around a symmetric product take the flag too: the diagonal and the thin mirror list have no twin, and
+// the float product rounds their doubles in registers
 void launch_spmv(SpmvFamily family, int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a,
                  const XcdSplit &xs, bool f32 = false);
 void spmv_allow_lds(SpmvFamily family, size_t bytes);      // dynamic LDS beyond the default 64 KB
 // the steps around the row-block launches, for `nvec` vectors at once (gridDim.y; vector j of x at x + j * ldx,
 // of y at y + j * ldy, its carry slots at carry + j * n_carry)
 void launch_sym_init(void *stream, int nvec, double *y, size_t ldy, const double *x, size_t ldx, const double *dvalues,
-                     size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha, double beta);
+                     size_t lo, size_t hi, size_t own_lo, size_t own_hi, double alpha, double beta, bool f32 = false);
 void launch_sym_mirror_rows(void *stream, int nvec, const uint32_t *rows, const uint32_t *ptr, const uint32_t *col,
                             const double *val, const double *x, size_t ldx, double *y, size_t ldy, double alpha,
-                            uint32_t n);
+                            uint32_t n, bool f32 = false);
 void launch_scale(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta);
 void launch_fixup(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
                   uint32_t n_carry, double *y, size_t ldy, double alpha, double beta, const double *dvalues,
-                  const double *x, size_t ldx);
+                  const double *x, size_t ldx, bool f32 = false);
 void launch_symfix(void *stream, const uint32_t *fix_ptr, const uint32_t *fix_idx, const double *spill, double *y,
                    double alpha, size_t nrows);
 
 // spmv_sx_kernels.hip
 void launch_spmv_sx(int waves, unsigned blocks, size_t lds_bytes, void *stream, const KernelArgs &a, const XcdSplit &xs,
-                    const uint32_t *sx_tab);
+                    const uint32_t *sx_tab, bool f32 = false);
 size_t spmv_sx_header_bytes(uint32_t pass_stride);
 void spmv_sx_allow_lds(size_t bytes);
 

@@ -33,19 +33,24 @@ namespace spx {
 // repeats the first where W <= 2: a strictly lower segment never reaches x[row], so col + 3 <= row stays
 // inside x for W >= 3, col + 1 <= row for W = 1).  The same number of loads for every pass lets passes of
 // different widths follow each other in one pipeline, and lets the compiler count its loads.
-template <int B>
+// V: the type of the values, double or float (the float twin, spx.gpu.values_f32: a.values then points at floats) --
+// the two value loads are 8 bytes wide then, at the same element offsets (W = 1: at any 4-byte aligned address,
+// spx_f2u_t), and hold the same one or two elements each; the second element of a W = 1 or 3 load is never used,
+// and lies inside the twin because the twin has as many elements as the doubles have room for.
+template <int B, class V = double>
 struct SxStage {
     uint32_t col[B];           // (wave-uniform) first column of lane 0's segment
     uint32_t geo[B];           // (wave-uniform) row of lane 0 | drow << 11 | (dcol + 128) << 18
     uint32_t slot[B];          // (wave-uniform) slot of lane 0's first column, or SPX_NO_SLOT
     uint32_t nw[B];            // (wave-uniform) nseg | width << 8
-    spx_d2u_t va[B], vb[B], xa[B], xb[B];
+    typename ValueVec<V>::pair_u va[B], vb[B];
+    spx_d2u_t xa[B], xb[B];
     double xr[B];
 };
 
-template <int B>
+template <int B, class V = double>
 __device__ __forceinline__ void sx_issue(const KernelArgs &a, const SpxRowBlock &rb, const PassWords (&ps)[B],
-                                         SxStage<B> &S, int lane)
+                                         SxStage<B, V> &S, int lane)
 {
 #pragma unroll
     for (int b = 0; b < B; ++b) {
@@ -56,11 +61,11 @@ __device__ __forceinline__ void sx_issue(const KernelArgs &a, const SpxRowBlock 
         S.geo[b] = geo;
         S.slot[b] = ps[b].w[3];
         S.nw[b] = ps[b].w[4] & 0xffffu;
-        const double *vals = a.values + rb.val_off + ps[b].val_off();
+        const V *vals = reinterpret_cast<const V *>(a.values) + rb.val_off + ps[b].val_off();
         const uint32_t off_a = W == 1u ? l : 2u * l;
         const uint32_t off_b = W == 3u ? 2u * nseg + l : (W == 4u ? 2u * nseg + 2u * l : off_a);
-        S.va[b] = *reinterpret_cast<const spx_d2u_t *>(vals + off_a);
-        S.vb[b] = *reinterpret_cast<const spx_d2u_t *>(vals + off_b);
+        S.va[b] = *reinterpret_cast<const typename ValueVec<V>::pair_u *>(vals + off_a);
+        S.vb[b] = *reinterpret_cast<const typename ValueVec<V>::pair_u *>(vals + off_b);
         const int drow = (int) ((geo >> 11) & 127u), dcol = (int) ((geo >> 18) & 255u) - 128;
         const uint32_t row = (geo & 2047u) + l * (uint32_t) drow;
         const double *xp = a.x + (S.col[b] + (uint32_t) ((int) l * dcol));
@@ -78,11 +83,15 @@ __device__ __forceinline__ void sx_issue(const KernelArgs &a, const SpxRowBlock 
 
 // ... and what follows once they have arrived: W FMAs and one LDS add for the row, W LDS adds of the
 // transposed products for the columns (or, without slots, W global atomics)
-template <int W>
+template <int W, class VP>
 __device__ __forceinline__ void sx_finish_pass(const KernelArgs &a, uint32_t col0, uint32_t geo, uint32_t slot0,
-                                               uint32_t nw, spx_d2u_t va, spx_d2u_t vb, spx_d2u_t xa, spx_d2u_t xb,
+                                               uint32_t nw, VP va_, VP vb_, spx_d2u_t xa, spx_d2u_t xb,
                                                double xr, double *slots, double *tile, int lane)
 {
+    // (floats widen here; doubles pass through)
+    spx_d2u_t va, vb;
+    va.x = (double) va_.x; va.y = (double) va_.y;
+    vb.x = (double) vb_.x; vb.y = (double) vb_.y;
     double t = va.x * xa.x;
     if (W >= 2) t = fma(va.y, xa.y, t);
     if (W >= 3) t = fma(vb.x, xb.x, t);
@@ -115,8 +124,8 @@ __device__ __forceinline__ void sx_finish_pass(const KernelArgs &a, uint32_t col
     }
 }
 
-template <int B>
-__device__ __forceinline__ void sx_finish(const KernelArgs &a, const SxStage<B> &S, double *slots, double *tile, int lane)
+template <int B, class V = double>
+__device__ __forceinline__ void sx_finish(const KernelArgs &a, const SxStage<B, V> &S, double *slots, double *tile, int lane)
 {
 #pragma unroll
     for (int b = 0; b < B; ++b) {
@@ -144,48 +153,49 @@ __device__ __forceinline__ void sx_headers(const uint32_t *hdr, int hi, int t, P
     }
 }
 
-template <int WAVES, int B>
+template <int WAVES, int B, class V = double>
 __device__ __forceinline__ void sx_run(const KernelArgs &a, const SpxRowBlock &rb, const uint32_t *hdr, int hi,
-                                       int n_in, int &t, SxStage<B> &A, double *slots, double *tile, int lane)
+                                       int n_in, int &t, SxStage<B, V> &A, double *slots, double *tile, int lane)
 {
-    SxStage<B> N;
+    SxStage<B, V> N;
     PassWords c[B];
     const int n_rounds = (n_in + B - 1) / B, t_end = t + n_in * WAVES;
     int r = 1;
     for (; r + 1 < n_rounds; r += 2) {
         t += B * WAVES;
         sx_headers<WAVES, B>(hdr, hi, t, c);
-        sx_issue<B>(a, rb, c, N, lane);
-        sx_finish<B>(a, A, slots, tile, lane);
+        sx_issue<B, V>(a, rb, c, N, lane);
+        sx_finish<B, V>(a, A, slots, tile, lane);
         t += B * WAVES;
         sx_headers<WAVES, B>(hdr, hi, t, c);
-        sx_issue<B>(a, rb, c, A, lane);
-        sx_finish<B>(a, N, slots, tile, lane);
+        sx_issue<B, V>(a, rb, c, A, lane);
+        sx_finish<B, V>(a, N, slots, tile, lane);
     }
     if (r < n_rounds) {
         t += B * WAVES;
         sx_headers<WAVES, B>(hdr, hi, t, c);
-        sx_issue<B>(a, rb, c, N, lane);
-        sx_finish<B>(a, A, slots, tile, lane);
-        sx_finish<B>(a, N, slots, tile, lane);
+        sx_issue<B, V>(a, rb, c, N, lane);
+        sx_finish<B, V>(a, A, slots, tile, lane);
+        sx_finish<B, V>(a, N, slots, tile, lane);
     } else {
-        sx_finish<B>(a, A, slots, tile, lane);
+        sx_finish<B, V>(a, A, slots, tile, lane);
     }
     t = t_end;
 }
 
 // a pass that is not an SX pass, on its own: the code of the plain kernels
+template <class V = double>
 __device__ __forceinline__ void sx_other(const KernelArgs &a, const SpxRowBlock &rb, const SpxPass &ps, double *slots,
                                          double *tile, const double *win, int lane)
 {
     if (ps.kind == SPX_PASS_SYMSEG) {
-        if (!abl::sym_no_mixed) run_symseg(a, rb, ps, slots, tile, lane);
+        if (!abl::sym_no_mixed) run_symseg<V>(a, rb, ps, slots, tile, lane);
     } else {
-        run_pass(a, rb, ps, tile, win, lane);
+        run_pass<1, V>(a, rb, ps, tile, win, lane);
     }
 }
 
-template <int WAVES, int B>
+template <int WAVES, int B, class V = double>
 __device__ __forceinline__ void spmv_body_sx(const KernelArgs &a, const XcdSplit &xs, const uint32_t *sx_tab, double *lds)
 {
     constexpr int BLOCK_THREADS = 64 * WAVES;
@@ -242,16 +252,16 @@ __device__ __forceinline__ void spmv_body_sx(const KernelArgs &a, const XcdSplit
     const int n_pass = rb.n_pass;
     int t = wave;
     const int n_first = t < hi ? (hi - 1 - t) / WAVES + 1 : 0;
-    SxStage<B> A;
+    SxStage<B, V> A;
     if (n_first > 0) {
 #pragma unroll
         for (int b = 1; b < B; ++b)
             if (t + b * WAVES >= hi) c[b] = no_pass(c[0]);
-        sx_issue<B>(a, rb, c, A, lane);
+        sx_issue<B, V>(a, rb, c, A, lane);
     }
     __syncthreads();
 
-    if (n_first > 0) sx_run<WAVES, B>(a, rb, hdr, hi, n_first, t, A, slots, tile, lane);
+    if (n_first > 0) sx_run<WAVES, B, V>(a, rb, hdr, hi, n_first, t, A, slots, tile, lane);
     // what is left: read-once passes of several units, unit passes of the mirrored part, leftovers
     while (t < n_pass) {
         const SpxPass p0 = lds_pass(hdr, t).pass();
@@ -259,12 +269,12 @@ __device__ __forceinline__ void spmv_body_sx(const KernelArgs &a, const XcdSplit
         if (two) {
             const SpxPass p1 = lds_pass(hdr, t + WAVES).pass();
             if (!(p0.kind == SPX_PASS_SYMSEG && p1.kind == SPX_PASS_SYMSEG &&
-                  (abl::sym_no_mixed || run_symseg2(a, rb, p0, p1, slots, tile, lane)))) {
-                sx_other(a, rb, p0, slots, tile, win, lane);
-                sx_other(a, rb, p1, slots, tile, win, lane);
+                  (abl::sym_no_mixed || run_symseg2<V>(a, rb, p0, p1, slots, tile, lane)))) {
+                sx_other<V>(a, rb, p0, slots, tile, win, lane);
+                sx_other<V>(a, rb, p1, slots, tile, win, lane);
             }
         } else {
-            sx_other(a, rb, p0, slots, tile, win, lane);
+            sx_other<V>(a, rb, p0, slots, tile, win, lane);
         }
         t += 2 * WAVES;
     }
@@ -280,7 +290,7 @@ __device__ __forceinline__ void spmv_body_sx(const KernelArgs &a, const XcdSplit
         // beta * y; the init pass leaves them out
         for (int i = threadIdx.x; i < n_rows; i += BLOCK_THREADS) {
             const size_t g = (size_t) rb.row0 + i;
-            double tt = a.alpha * (tile[i] + a.dvalues_priv[g] * a.x[g]);
+            double tt = a.alpha * (tile[i] + stored_as<V>(a.dvalues_priv[g]) * a.x[g]);
             if (a.beta_priv != 0.0) tt += a.beta_priv * a.y[g];
             a.y[g] = tt;
         }
@@ -302,6 +312,16 @@ void csx_spmv_sx_kernel(SPX_KERNEL_PARAMS, const uint32_t *sx_tab_)
     spmv_body_sx<WAVES, B>(a, xcd_split, sx_tab_, lds_dyn);
 }
 
+// ... on the float twin of the values (spx_hip_matvec_kernel_f32 on a symmetric handle)
+template <int WAVES, int B>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_sx_f32_kernel(SPX_KERNEL_PARAMS, const uint32_t *sx_tab_)
+{
+    SPX_KERNEL_ARGS(a);
+    extern __shared__ double lds_dyn[];
+    spmv_body_sx<WAVES, B, float>(a, xcd_split, sx_tab_, lds_dyn);
+}
+
 // (B: passes per round of the pipeline.  Two per round -- the unit-window kernel's choice -- take 90 VGPRs, five
 // wavefronts per SIMD, and measured 3-4 % slower than one per round at 64 VGPRs: 947 / 939 against 913 / 903 us on
 // the bench matrix, profiles/r06/sx_order_and_width_raw.md; three workgroups of eight wavefronts per CU with one
@@ -309,18 +329,20 @@ void csx_spmv_sx_kernel(SPX_KERNEL_PARAMS, const uint32_t *sx_tab_)
 constexpr int SX_PASSES_PER_ROUND = 1;
 
 void launch_spmv_sx(int waves, unsigned blocks, size_t lds_bytes, void *stream_, const KernelArgs &a, const XcdSplit &xs,
-                    const uint32_t *sx_tab)
+                    const uint32_t *sx_tab, bool f32)
 {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-#define SPX_LAUNCH_SX(W)                                                                              \
-    hipLaunchKernelGGL((csx_spmv_sx_kernel<W, SX_PASSES_PER_ROUND>), dim3(blocks), dim3(64 * W), lds_bytes, stream, a.rbs,  \
+#define SPX_LAUNCH_SX_(KERNEL, W)                                                                     \
+    hipLaunchKernelGGL((KERNEL<W, SX_PASSES_PER_ROUND>), dim3(blocks), dim3(64 * W), lds_bytes, stream, a.rbs,  \
                        a.passes, a.n_rb, a.pass_stride, xs, a.values, a.descs, a.cidx, a.segrows,   \
                        a.x, a.y, a.carry, a.dvalues, a.spill, a.slot_col, a.alpha, a.beta,           \
                        a.dvalues_priv, a.beta_priv, sx_tab)
+#define SPX_LAUNCH_SX(W) do { if (f32) SPX_LAUNCH_SX_(csx_spmv_sx_f32_kernel, W); else SPX_LAUNCH_SX_(csx_spmv_sx_kernel, W); } while (0)
     if (waves == 2) SPX_LAUNCH_SX(2);
     else if (waves == 8) SPX_LAUNCH_SX(8);
     else SPX_LAUNCH_SX(4);
 #undef SPX_LAUNCH_SX
+#undef SPX_LAUNCH_SX_
 }
 
 // the LDS a launch needs beyond the plain read-once kernel's: the pass headers (and the alignment in front)
@@ -332,7 +354,8 @@ size_t spmv_sx_header_bytes(uint32_t pass_stride)
 void spmv_sx_allow_lds(size_t bytes)
 {
     const int b = (int) bytes;
-#define SPX_ATTR_SX(W) (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_sx_kernel<W, SX_PASSES_PER_ROUND>), hipFuncAttributeMaxDynamicSharedMemorySize, b)
+#define SPX_ATTR_SX(W) (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_sx_kernel<W, SX_PASSES_PER_ROUND>), hipFuncAttributeMaxDynamicSharedMemorySize, b); \
+    (void) hipFuncSetAttribute(reinterpret_cast<const void *>(&csx_spmv_sx_f32_kernel<W, SX_PASSES_PER_ROUND>), hipFuncAttributeMaxDynamicSharedMemorySize, b)
     SPX_ATTR_SX(2); SPX_ATTR_SX(4); SPX_ATTR_SX(8);
 #undef SPX_ATTR_SX
 }

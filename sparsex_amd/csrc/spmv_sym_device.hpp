@@ -43,6 +43,9 @@ __device__ __forceinline__ double xchg4(double v)
 // eight lanes (4 + 2 + 1 values travel), so that each lane ends up with ONE
 // column and the LDS adds of a tile hit eight different addresses -- lanes
 // that add to the same address are serialised at ~3 clocks each.
+// V (here and in the read-once segments below): the type of the stream's values, as in spmv_device.hpp -- double,
+// or float for the products on the float twin (a.values then points at floats): the same loads at the same element
+// offsets and half the width, widened in registers; every product, sum, exchange and atomic is fp64 either way.
 // the lane's tile descriptor of a tile pass: {col0, row0 | slot << 9}
 __device__ __forceinline__ uint2 symtile_desc(const KernelArgs &a, const SpxRowBlock &rb, const SpxPass &ps, int lane)
 {
@@ -53,6 +56,7 @@ __device__ __forceinline__ uint2 symtile_desc(const KernelArgs &a, const SpxRowB
 // (`q`: the lane's tile descriptor, fetched by the caller -- a wavefront that runs several tile passes in a row
 // asks for the next pass' descriptors together with the values of the current one: one memory round trip per
 // pass instead of two, symtile_run below)
+template <class V = double>
 __device__ __forceinline__ void symtile_pass(const KernelArgs &a, const SpxRowBlock &rb,
                                              const SpxPass &ps, const uint2 q, double *slots, double *tile,
                                              int lane)
@@ -60,11 +64,11 @@ __device__ __forceinline__ void symtile_pass(const KernelArgs &a, const SpxRowBl
     const uint32_t nseg = ps.nseg;
     const bool active = (uint32_t) lane < nseg;
     const uint32_t l = active ? (uint32_t) lane : 0u;
-    const double *vals = a.values + rb.val_off + ps.val_off;
-    double2 v2[4];
+    const V *vals = reinterpret_cast<const V *>(a.values) + rb.val_off + ps.val_off;
+    typename ValueVec<V>::pair v2[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
-        v2[p] = ld_stream(reinterpret_cast<const double2 *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
+        v2[p] = ld_stream(reinterpret_cast<const typename ValueVec<V>::pair *>(vals + (uint32_t) p * 2u * nseg + l * 2u));
     const int i = (int) (l & 7u);
     const int row = (int) (ps.elem0 + (q.y & 511u)) + i;
     const uint32_t slot = q.y >> 9;
@@ -73,8 +77,8 @@ __device__ __forceinline__ void symtile_pass(const KernelArgs &a, const SpxRowBl
     double v[8], t = 0.0, p8[8];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        v[2 * p] = v2[p].x;
-        v[2 * p + 1] = v2[p].y;
+        v[2 * p] = (double) v2[p].x;
+        v[2 * p + 1] = (double) v2[p].y;
     }
     // (tiles start on columns that are multiples of eight: where x itself is 16-byte
     // aligned the eight x values of the tile come as four 16-byte loads)
@@ -135,10 +139,11 @@ __device__ __forceinline__ void symtile_pass(const KernelArgs &a, const SpxRowBl
     }
 }
 
+template <class V = double>
 __device__ __forceinline__ void symtile_pass(const KernelArgs &a, const SpxRowBlock &rb, const SpxPass &ps,
                                              double *slots, double *tile, int lane)
 {
-    symtile_pass(a, rb, ps, symtile_desc(a, rb, ps, lane), slots, tile, lane);
+    symtile_pass<V>(a, rb, ps, symtile_desc(a, rb, ps, lane), slots, tile, lane);
 }
 
 // The tile passes at the head of a wavefront's list (pass t, t + WAVES, ... while they are tile passes; the
@@ -149,7 +154,7 @@ __device__ __forceinline__ void symtile_pass(const KernelArgs &a, const SpxRowBl
 // requested in front of the loads of the current one, the pass header a pass further ahead still.
 // `p0` / `p1`: the headers of the passes t and t + WAVES, already loaded.  On return t is the wavefront's next
 // pass (not a tile pass, or past the end) and p0 / p1 are its header and the one WAVES behind it.
-template <int WAVES>
+template <int WAVES, class V = double>
 __device__ __forceinline__ void symtile_run(const KernelArgs &a, const SpxRowBlock &rb, const SpxPass *passes, int n_pass,
                                             int &t, SpxPass &p0, SpxPass &p1, double *slots, double *tile, int lane)
 {
@@ -159,7 +164,7 @@ __device__ __forceinline__ void symtile_run(const KernelArgs &a, const SpxRowBlo
         const bool more = t + WAVES < n_pass && p1.kind == SPX_PASS_SYMTILE;         // (wave-uniform)
         const SpxPass p2 = passes[t + 2 * WAVES];                                    // (the table is padded)
         const uint2 qn = symtile_desc(a, rb, more ? p1 : p0, lane);
-        symtile_pass(a, rb, p0, q, slots, tile, lane);
+        symtile_pass<V>(a, rb, p0, q, slots, tile, lane);
         t += WAVES;
         p0 = p1;
         p1 = p2;
@@ -174,7 +179,7 @@ __device__ __forceinline__ void symtile_run(const KernelArgs &a, const SpxRowBlo
 // addresses; lanes of neighbouring rows mostly hit different ones) -- every value is read
 // once and used twice.  A segment without slots adds straight to y (global atomics; the
 // kernel's hand-over is atomic anyway).
-template <int W, int B>
+template <int W, int B, class V = double>
 __device__ __forceinline__ void symseg_passes(const KernelArgs &a, const SpxRowBlock &rb,
                                               const SpxPass (&ps)[B], double *slots, double *tile, int lane)
 {
@@ -206,14 +211,15 @@ __device__ __forceinline__ void symseg_passes(const KernelArgs &a, const SpxRowB
     double v[B][W];
 #pragma unroll
     for (int b = 0; b < B; ++b) {
-        const double *vals = a.values + rb.val_off + ps[b].val_off;
+        const V *vals = reinterpret_cast<const V *>(a.values) + rb.val_off + ps[b].val_off;
 #pragma unroll
         for (int p = 0; p < W / 2; ++p) {
-            const double2 vv = ld_stream(reinterpret_cast<const double2 *>(vals + (uint32_t) p * 2u * nseg[b] + l[b] * 2u));
-            v[b][2 * p] = vv.x;
-            v[b][2 * p + 1] = vv.y;
+            const typename ValueVec<V>::pair vv =
+                ld_stream(reinterpret_cast<const typename ValueVec<V>::pair *>(vals + (uint32_t) p * 2u * nseg[b] + l[b] * 2u));
+            v[b][2 * p] = (double) vv.x;
+            v[b][2 * p + 1] = (double) vv.y;
         }
-        if (W & 1) v[b][W - 1] = ld_stream(vals + (uint32_t) (W / 2) * 2u * nseg[b] + l[b]);
+        if (W & 1) v[b][W - 1] = (double) ld_stream(vals + (uint32_t) (W / 2) * 2u * nseg[b] + l[b]);
     }
     int row[B], sdc[B];
     uint32_t col[B];
@@ -263,30 +269,32 @@ __device__ __forceinline__ void symseg_passes(const KernelArgs &a, const SpxRowB
     }
 }
 
+template <class V = double>
 __device__ __forceinline__ void run_symseg(const KernelArgs &a, const SpxRowBlock &rb, const SpxPass &ps,
                                            double *slots, double *tile, int lane)
 {
     switch (ps.width) {            // wave-uniform
-    case 2: symseg_passes<2, 1>(a, rb, {ps}, slots, tile, lane); break;
-    case 3: symseg_passes<3, 1>(a, rb, {ps}, slots, tile, lane); break;
-    case 4: symseg_passes<4, 1>(a, rb, {ps}, slots, tile, lane); break;
-    case 5: symseg_passes<5, 1>(a, rb, {ps}, slots, tile, lane); break;
-    case 6: symseg_passes<6, 1>(a, rb, {ps}, slots, tile, lane); break;
-    case 7: symseg_passes<7, 1>(a, rb, {ps}, slots, tile, lane); break;
-    default: symseg_passes<8, 1>(a, rb, {ps}, slots, tile, lane); break;
+    case 2: symseg_passes<2, 1, V>(a, rb, {ps}, slots, tile, lane); break;
+    case 3: symseg_passes<3, 1, V>(a, rb, {ps}, slots, tile, lane); break;
+    case 4: symseg_passes<4, 1, V>(a, rb, {ps}, slots, tile, lane); break;
+    case 5: symseg_passes<5, 1, V>(a, rb, {ps}, slots, tile, lane); break;
+    case 6: symseg_passes<6, 1, V>(a, rb, {ps}, slots, tile, lane); break;
+    case 7: symseg_passes<7, 1, V>(a, rb, {ps}, slots, tile, lane); break;
+    default: symseg_passes<8, 1, V>(a, rb, {ps}, slots, tile, lane); break;
     }
 }
 
 // two read-once passes of the same width (<= 4: the registers of two wider ones would cost
 // the kernel its eight wavefronts per SIMD) side by side
+template <class V = double>
 __device__ __forceinline__ bool run_symseg2(const KernelArgs &a, const SpxRowBlock &rb, const SpxPass &p0,
                                             const SpxPass &p1, double *slots, double *tile, int lane)
 {
     if (p0.width != p1.width || p0.width > 4) return false;
     switch (p0.width) {
-    case 2: symseg_passes<2, 2>(a, rb, {p0, p1}, slots, tile, lane); break;
-    case 3: symseg_passes<3, 2>(a, rb, {p0, p1}, slots, tile, lane); break;
-    default: symseg_passes<4, 2>(a, rb, {p0, p1}, slots, tile, lane); break;
+    case 2: symseg_passes<2, 2, V>(a, rb, {p0, p1}, slots, tile, lane); break;
+    case 3: symseg_passes<3, 2, V>(a, rb, {p0, p1}, slots, tile, lane); break;
+    default: symseg_passes<4, 2, V>(a, rb, {p0, p1}, slots, tile, lane); break;
     }
     return true;
 }

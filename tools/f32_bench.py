@@ -3,6 +3,10 @@
 product in the same process.  One matrix per process:
 
     python3 tools/f32_bench.py --matrix nlpkkt [--edge 150] | --matrix cant | --matrix webbase  [--out FILE]
+    python3 tools/f32_bench.py --symmetric --matrix nlpkkt [--edge 150] | --matrix nd24k | --matrix cant  [--out FILE]
+
+--symmetric tunes the matrix as a symmetric one (spx.matrix.symmetric=true) and asks for the copy with
+spx.gpu.values_f32=all ("true" where it is not given); the bytes are then those of the stored triangle and the diagonal.
 
 Variants, timed with HIP events on one stream after a warm-up call, alternating inside every one of the 5 batches
 (bench.py's BATCHES; about 50 ms of work per batch and variant; the median per variant is reported):
@@ -31,7 +35,7 @@ sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402  (make_workload, tune, ALPHA, BATCHES, HBM_PEAK_GBS: the bench protocol)
 
-MATRICES = {"nlpkkt": "syn-nlpkkt", "cant": "syn-cant", "webbase": "syn-webbase"}
+MATRICES = {"nlpkkt": "syn-nlpkkt", "cant": "syn-cant", "webbase": "syn-webbase", "nd24k": "syn-nd24k"}
 
 
 def workload(name, edge):
@@ -51,6 +55,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--matrix", choices=list(MATRICES), required=True)
     ap.add_argument("--edge", type=int, default=bench.SAMPLE_EDGE, help="grid edge of syn-nlpkkt")
+    ap.add_argument("--symmetric", action="store_true",
+                    help="tune as a symmetric matrix, the copy asked for with spx.gpu.values_f32=all")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--first", choices=["without", "with"], default="without",
                     help="which handle is tuned first and whose fp64 product is timed first in every batch (the two run "
@@ -71,6 +77,9 @@ def main():
     n, nnz = csr[3], int(csr[0][-1])
     note("%s: %d rows, %d nonzeros" % (MATRICES[args.matrix], n, nnz))
     base = {"spx.rt.nr_threads": args.threads, "spx.rt.device": 0, "spx.rt.keep_encoded": "false"}
+    if args.symmetric:
+        base["spx.matrix.symmetric"] = "true"
+    on = "all" if args.symmetric else "true"
     tunes = {}
 
     def tuned(name, extra):
@@ -81,10 +90,11 @@ def main():
         return A
     if args.first == "without":
         A0 = tuned("values_f32=false", {"spx.gpu.values_f32": "false"})
-        A1 = tuned("values_f32=true", {"spx.gpu.values_f32": "true"})
+        A1 = tuned("values_f32=" + on, {"spx.gpu.values_f32": on})
     else:
-        A1 = tuned("values_f32=true", {"spx.gpu.values_f32": "true"})
+        A1 = tuned("values_f32=" + on, {"spx.gpu.values_f32": on})
         A0 = tuned("values_f32=false", {"spx.gpu.values_f32": "false"})
+    assert bool(A0.info().symmetric) == bool(A1.info().symmetric) == args.symmetric
     assert A0.values_f32_bytes() == 0 and A1.values_f32_bytes() > 0
     xh = synth.random_x(n, seed=42)
     x = torch.from_numpy(xh).to(dev)
@@ -144,11 +154,15 @@ def main():
 
     def form(i):
         return {"waves": int(i.waves), "unit_windows": int(i.unit_windows), "wave_tiles": int(i.wave_tiles),
-                "col_slices": int(i.col_slices), "rowblocks": int(i.n_rowblocks)}
-    bytes_64 = bench.algorithmic_bytes(False, nnz, n, n)
-    bytes_32 = bytes_64 - 4.0 * nnz
+                "col_slices": int(i.col_slices), "rowblocks": int(i.n_rowblocks), "sym_tiles": int(i.sym_tiles),
+                "sym_segments": int(i.sym_segments), "sym_pipeline": int(i.sym_pipeline)}
+    # (symmetric: the strictly lower values and the diagonal are stored; the float product reads the former as
+    # floats, the diagonal stays an array of doubles)
+    lower = (nnz - n) // 2
+    bytes_64 = bench.algorithmic_bytes(args.symmetric, nnz, n, n, lower)
+    bytes_32 = bytes_64 - 4.0 * (lower if args.symmetric else nnz)
     spread = {k: [round(1e6 * min(v), 2), round(1e6 * max(v), 2)] for k, v in per.items()}
-    out = {"matrix": MATRICES[args.matrix], "edge": args.edge if args.matrix == "nlpkkt" else None, "nrows": n, "nnz": nnz,
+    out = {"matrix": MATRICES[args.matrix], "symmetric": bool(args.symmetric), "edge": args.edge if args.matrix == "nlpkkt" else None, "nrows": n, "nnz": nnz,
            "value_mb": round(int(i1.value_bytes) / 1e6, 1), "values_f32_mb": round(A1.values_f32_bytes() / 1e6, 1),
            "launch_form": {"f64-plain": form(i0), "f64": form(i1)}, "order": list(calls),
            "us": {k: round(1e6 * v, 2) for k, v in t.items()}, "us_spread": spread,
