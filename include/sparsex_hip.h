@@ -348,7 +348,35 @@ spx_error_t spx_hip_vec_scale_add_ratio(const spx_hip_vec_t *v1, const spx_hip_v
 spx_error_t spx_hip_vec_cg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_hip_vec_t *r,
                                   const spx_hip_vec_t *ap, spx_value_t *rr_dev,
                                   const spx_value_t *pap_dev, spx_value_t *beta_dev, void *stream);
-/* Diagnostic: a read stream with the stores of an SpMV in it.  `src` is read in chunks of `chunk_doubles` (a
+/* ---- a diagonal preconditioner: elementwise helpers and the fused Jacobi-PCG step.  All four calls only enqueue
+ * on `stream`: no allocation, no copy to the host, no synchronisation; all are legal during stream capture. */
+/* v3 <- v1 .* v2 (one IEEE multiplication per element; v3 may be v1 or v2) */
+spx_error_t spx_hip_vec_mul_elem(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, spx_hip_vec_t *v3, void *stream);
+/* v2 <- 1 / v1 elementwise (IEEE division), if_zero where v1 is +-0; v2 may be v1.  With spx_hip_mat_get_diag_vec
+ * in front of it: the Jacobi preconditioner of the matrix (rows without a diagonal entry get if_zero). */
+spx_error_t spx_hip_vec_reciprocal(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, spx_value_t if_zero, void *stream);
+/* One preconditioned CG update in one pass over the vectors, minv any diagonal preconditioner:
+ *   a = *rz_dev / *pap_dev (0 if *pap_dev == 0);  x += a*p;  r -= a*ap;
+ *   z_i = minv_i * r_i (one rounded multiplication; z is not stored);
+ *   rz_new = sum z_i*r_i;  rr_new = sum r_i*r_i   (both in a fixed order: reproducible)
+ *   *beta_dev = rz_new / *rz_dev (0 if *rz_dev == 0);  *rz_dev = rz_new;  *rr_dev = rr_new.
+ * x, r and *rr_dev get the bits spx_hip_vec_cg_update gives x, r and its rr for the same a.  p, ap and minv are
+ * read only.  One iteration of Jacobi-PCG is a product (ap <- A p), spx_hip_vec_mul_dev(p, ap, pap_dev), this call
+ * and spx_hip_vec_pcg_direction.  With *rz_dev = *pap_dev = 0 the call leaves x and r alone and writes
+ * rz = z.r, rr = r.r and beta = 0: the start-up call, followed by spx_hip_vec_pcg_direction(p, r, minv, NULL).
+ * With r = p = 0 nothing becomes NaN.
+ * Refused with SPX_FAILURE through the error handler, nothing enqueued and every input untouched: vectors of
+ * different sizes; x, p, r, ap, minv not five different vectors; rz_dev, pap_dev, beta_dev, rr_dev not four
+ * different addresses; a scalar inside x or r; a NULL scalar or vector. */
+spx_error_t spx_hip_vec_pcg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_hip_vec_t *r, const spx_hip_vec_t *ap,
+                                   const spx_hip_vec_t *minv, spx_value_t *rz_dev, const spx_value_t *pap_dev,
+                                   spx_value_t *beta_dev, spx_value_t *rr_dev, void *stream);
+/* p <- minv .* r + (*beta_dev) * p: the bits of spx_hip_vec_mul_elem(minv, r, z) followed by
+ * spx_hip_vec_scale_add(z, p, p, *beta_dev), without z.  beta_dev == NULL: p <- minv .* r (the bits of z).
+ * Refused as above: different sizes; p, r, minv not three different vectors; beta_dev inside p; a NULL vector. */
+spx_error_t spx_hip_vec_pcg_direction(spx_hip_vec_t *p, const spx_hip_vec_t *r, const spx_hip_vec_t *minv,
+                                      const spx_value_t *beta_dev, void *stream);
+/* Diagnostic: a read stream with the stores of an SpMV in it. `src` is read in chunks of `chunk_doubles` (a
  * multiple of 2048), one per workgroup, workgroup b on XCD b % 8 as the SpMV kernels' row-blocks; every workgroup
  * then stores `write_doubles` doubles to its stretch of `dst` (dst->size >= chunks * write_doubles).  Timed by
  * the caller; what bench.py prints as roofline.measured_mixed_peak. */
@@ -660,6 +688,55 @@ typedef struct {
     uint64_t plan_bytes;          /* HBM the plan occupies (0 on a host-only matrix)                           */
 } spx_hip_values_plan_t;
 spx_error_t spx_hip_mat_values_plan_get(const spx_matrix_t *A, spx_hip_values_plan_t *plan);
+
+/* The diagonal of a tuned matrix, for a Jacobi preconditioner (spx_hip_vec_reciprocal, spx_hip_vec_pcg_update):
+ * read from the values as they are NOW -- after spx_hip_mat_set_values they may exist only in HBM -- and in the
+ * numbering of the products' vectors, which is the tuned one under SPX_MAT_REORDER / spx.rt.dist_reorder.  The
+ * reference hands out one entry per call (spx_mat_get_entry, src/api/matvec.c:340-374).
+ *
+ *  - spx_hip_mat_diag_plan (host side, once per tune or restore) finds in ONE walk over the descriptor stream,
+ *    on all host threads, the position of a(i, i) in the stream's value array for every own row i, or 0xffffffff.
+ *    It works on the index-only host copy of a matrix in HBM and on host-only matrices (spx.rt.host_only).  It
+ *    fails with SPX_FAILURE through the error handler when a diagonal entry lies at two positions or the value
+ *    array has 2^32 - 1 positions or more; a failed call leaves no plan behind, an earlier one included.
+ *  - The position array goes to HBM once: 4 bytes per own row (plan_bytes; 0 on a host-only matrix).  The call
+ *    leaves the calling thread's current device as it found it.
+ *  - Symmetric matrices keep their diagonal in an array of its own in HBM: the plan call succeeds and plans
+ *    nothing (pos == NULL, n_present == 0, plan_bytes == 0), and spx_hip_mat_get_diag* work without a plan call.
+ *  - The plan is not part of a saved matrix: after spx_mat_restore it is built again.  A second
+ *    spx_hip_mat_diag_plan replaces the first; spx_hip_mat_diag_plan_drop and spx_mat_destroy release it.
+ *  - spx_hip_mat_get_diag enqueues ONE kernel (csx_gather_diag_kernel) on `stream` (a hipStream_t): no
+ *    allocation, no wait, legal during stream capture.  It obeys the handle's single-stream rule: the stream
+ *    orders it with spx_hip_mat_set_values and the matrix' products.  It counts as "a product was enqueued since
+ *    the last edit" for spx_mat_set_entry's wait-once rule.
+ *  - `d_dev` holds nrows doubles in HBM of the matrix' device, 8-byte aligned (16-byte stores are used where the
+ *    address allows).  d[i] = a(i, i) for the own rows; +0.0 for a row without a stored diagonal entry and for a
+ *    row i >= ncols of a rectangular matrix.  A row slice (spx.rt.gpu_rank/world, spx.rt.row_offset) or an
+ *    attached matrix writes [row_lo, row_hi) and leaves the rest alone.
+ *  - It reads the doubles where they live: it sees what spx_hip_mat_set_values* and spx_mat_set_entry wrote, with
+ *    or without a float copy (spx.gpu.values_f32), in every column slice of spx.gpu.col_phases.
+ *  - spx_hip_mat_get_diag_vec: the same into a device vector of nrows elements.
+ *  - spx_hip_mat_get_diag_host is synchronous and takes a host array of nrows doubles: on a matrix in HBM through
+ *    a temporary device buffer, on a host-only matrix from the host copy of the stream.
+ *  - spx_hip_mat_get_diag* fail with SPX_FAILURE through the error handler, nothing enqueued and nothing written,
+ *    with a NULL handle or pointer, on a general matrix without a plan ("no diagonal plan"), when the calling
+ *    thread's current device is not the matrix' one, spx_hip_mat_get_diag[_vec] on a host-only matrix (use
+ *    _host), and _vec with a vector whose size is not nrows. */
+spx_error_t spx_hip_mat_diag_plan(spx_matrix_t *A);
+spx_error_t spx_hip_mat_diag_plan_drop(spx_matrix_t *A);
+spx_error_t spx_hip_mat_get_diag(const spx_matrix_t *A, spx_value_t *d_dev, void *stream);
+spx_error_t spx_hip_mat_get_diag_vec(const spx_matrix_t *A, spx_hip_vec_t *d, void *stream);
+spx_error_t spx_hip_mat_get_diag_host(const spx_matrix_t *A, spx_value_t *d);
+/* The plan, for inspection and tests: the array belongs to the matrix and lives until the next
+ * spx_hip_mat_diag_plan, spx_hip_mat_diag_plan_drop or spx_mat_destroy(). */
+typedef struct {
+    const uint32_t *pos;          /* per own row: position of a(i, i) in the stream's values, or 0xffffffff;
+                                     NULL on a symmetric matrix                                              */
+    size_t n_rows, row_lo;        /* own rows, the first of them                                             */
+    uint64_t n_present;           /* own rows with a stored diagonal entry (symmetric: 0, nothing is planned) */
+    uint64_t plan_bytes;          /* HBM the plan occupies (0 on host-only and symmetric matrices)           */
+} spx_hip_diag_plan_t;
+spx_error_t spx_hip_mat_diag_plan_get(const spx_matrix_t *A, spx_hip_diag_plan_t *plan);
 
 /* The same for a caller compiled against another revision of this header: at most `size` bytes
  * (the caller's sizeof(spx_hip_info_t)) are written -- the struct only ever grows at its end.

@@ -8,7 +8,7 @@ ctypes, plus helpers to hand HBM-resident torch tensors to the library.
 """
 from .api import (  # noqa: F401
     SpxError, lib, lib_path, Matrix, Input, option_set, options_reset,
-    input_load_csr, input_load_mmf, mat_tune, mat_restore, DeviceVector, matvec_kernel_vec, matvec_kernel_f32_vec, matvec_trans_kernel_vec, cg_update, matvec_kernel_csr,
+    input_load_csr, input_load_mmf, mat_tune, mat_restore, DeviceVector, matvec_kernel_vec, matvec_kernel_f32_vec, matvec_trans_kernel_vec, cg_update, pcg_update, pcg_direction, matvec_kernel_csr,
     vec_reorder, vec_inv_reorder, RcclTransport, CallbackTransport, rccl_unique_id,
     SPX_DIST_OWNED_ROWS, SPX_DIST_GATHER_Y, SPX_DIST_HALO_X, SPX_DIST_OVERLAP, dist_reorder,
     SPX_DIST_REORDER_RCM, SPX_DIST_REORDER_RCM_OWNER,

@@ -68,6 +68,11 @@ class ValuesPlan(C.Structure):
                 ("plan_bytes", C.c_uint64)]
 
 
+class DiagPlan(C.Structure):
+    _fields_ = [("pos", C.POINTER(C.c_uint32)), ("n_rows", C.c_size_t), ("row_lo", C.c_size_t),
+                ("n_present", C.c_uint64), ("plan_bytes", C.c_uint64)]
+
+
 class XwPlan(C.Structure):
     _fields_ = [("tab", C.POINTER(C.c_uint32)), ("xdescs", C.POINTER(C.c_uint32)), ("passes", C.c_void_p),
                 ("n_rowblocks", C.c_size_t), ("n_descs", C.c_size_t), ("n_passes", C.c_size_t),
@@ -177,6 +182,16 @@ def lib():
     L.spx_hip_mat_set_values.argtypes = [vp, vp, vp]
     L.spx_hip_mat_set_values_host.argtypes = [vp, vp]
     L.spx_hip_mat_values_plan_get.argtypes = [vp, C.POINTER(ValuesPlan)]
+    L.spx_hip_mat_diag_plan.argtypes = [vp]
+    L.spx_hip_mat_diag_plan_drop.argtypes = [vp]
+    L.spx_hip_mat_get_diag.argtypes = [vp, vp, vp]
+    L.spx_hip_mat_get_diag_vec.argtypes = [vp, vp, vp]
+    L.spx_hip_mat_get_diag_host.argtypes = [vp, vp]
+    L.spx_hip_mat_diag_plan_get.argtypes = [vp, C.POINTER(DiagPlan)]
+    L.spx_hip_vec_mul_elem.argtypes = [vp, vp, vp, vp]
+    L.spx_hip_vec_reciprocal.argtypes = [vp, vp, d, vp]
+    L.spx_hip_vec_pcg_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.spx_hip_vec_pcg_direction.argtypes = [vp, vp, vp, vp, vp]
     L.spx_log_disable_all.restype = None
     L.spx_log_error_console.restype = None
     _lib = L
@@ -617,6 +632,57 @@ class Matrix:
         st = stream if stream is not None else torch.cuda.current_stream(values.device)
         self.hip_set_values(values.data_ptr(), st.cuda_stream)
 
+    def diag_plan(self):
+        """``spx_hip_mat_diag_plan`` -- finds where the diagonal entries lie in the tuned stream, once per tune or
+        restore; `get_diag` / `get_diag_host` then read them.  A symmetric matrix needs none."""
+        if lib().spx_hip_mat_diag_plan(self.handle) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_diag_plan failed (see stderr)")
+
+    def diag_plan_drop(self):
+        """``spx_hip_mat_diag_plan_drop``."""
+        if lib().spx_hip_mat_diag_plan_drop(self.handle) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_diag_plan_drop failed")
+
+    def diag_plan_info(self):
+        """``spx_hip_mat_diag_plan_get``: pos as a numpy copy (uint32, 0xffffffff = no diagonal entry stored; None on
+        a symmetric matrix) and n_rows, row_lo, n_present, plan_bytes."""
+        pl = DiagPlan()
+        if lib().spx_hip_mat_diag_plan_get(self.handle, C.byref(pl)) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_diag_plan_get failed: no plan")
+        out = {k: int(getattr(pl, k)) for k in ("n_rows", "row_lo", "n_present", "plan_bytes")}
+        out["pos"] = np.ctypeslib.as_array(pl.pos, shape=(pl.n_rows,)).copy() if pl.pos and pl.n_rows else (
+            np.zeros(0, np.uint32) if pl.pos else None)
+        return out
+
+    def hip_get_diag(self, ptr, stream=0):
+        """``spx_hip_mat_get_diag`` -- the diagonal to the nrows doubles in HBM at `ptr` (enqueue only)."""
+        if lib().spx_hip_mat_get_diag(self.handle, ptr, stream) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_get_diag failed (see stderr)")
+
+    def get_diag(self, dst=None, stream=None):
+        """``spx_hip_mat_get_diag_vec`` -- the diagonal, in the numbering of the products' vectors, into the
+        DeviceVector `dst` (created when None) on `stream` (a raw hipStream_t or a torch stream; default the null
+        stream).  Returns the vector."""
+        if dst is None:
+            dst = DeviceVector(self.nrows)
+        st = 0 if stream is None else getattr(stream, "cuda_stream", stream)
+        handle = dst.handle if isinstance(dst, DeviceVector) else None
+        if lib().spx_hip_mat_get_diag_vec(self.handle, handle, st) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_get_diag_vec failed (see stderr)")
+        return dst
+
+    def get_diag_host(self, out=None):
+        """``spx_hip_mat_get_diag_host`` -- the diagonal as a numpy array of nrows doubles (synchronous; also for
+        host-only matrices).  A row slice writes its own rows of `out` and leaves the rest alone (a new array: 0)."""
+        if out is None:
+            out = np.zeros(self.nrows)
+        if out.dtype != np.float64 or out.ndim != 1 or out.size != self.nrows or not out.flags["C_CONTIGUOUS"]:
+            raise SpxError("get_diag_host: a contiguous float64 array of nrows elements")
+        keep = out if out.size else np.zeros(1)
+        if lib().spx_hip_mat_get_diag_host(self.handle, keep.ctypes.data) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_get_diag_host failed (see stderr)")
+        return out
+
     def get_perm(self):
         """``spx_mat_get_perm`` -- perm[old index] = new index of a matrix tuned with
         ``reorder=True``; ``None`` when the matrix was not reordered."""
@@ -726,6 +792,12 @@ class DeviceVector:
         self._check(lib().spx_hip_vec_scale_add_ratio(self.handle, other.handle, dst.handle, scale, nump, denp,
                                                       stream), "spx_hip_vec_scale_add_ratio")
 
+    def mul_elem_into(self, other, dst, stream=0):         # dst <- self .* other
+        self._check(lib().spx_hip_vec_mul_elem(self.handle, other.handle, dst.handle, stream), "spx_hip_vec_mul_elem")
+
+    def reciprocal_into(self, dst, if_zero=0.0, stream=0):    # dst <- 1 / self, if_zero where self is +-0
+        self._check(lib().spx_hip_vec_reciprocal(self.handle, dst.handle, if_zero, stream), "spx_hip_vec_reciprocal")
+
     def probe_read_write(self, dst, chunk_doubles, write_doubles, stream=0):
         """Diagnostic (spx_hip_probe_read_write): this vector read in chunks, `write_doubles` stored per chunk to dst."""
         L = lib()
@@ -777,6 +849,36 @@ def cg_update(x, p, r, ap, scalars, stream=0):
     rc = lib().spx_hip_vec_cg_update(x.handle, p.handle, r.handle, ap.handle, sp[0], sp[1], sp[2], stream)
     if rc != SPX_SUCCESS:
         raise SpxError("spx_hip_vec_cg_update failed (see stderr)")
+
+
+def pcg_update(x, p, r, ap, minv, scalars, stream=0):
+    """``spx_hip_vec_pcg_update``: a = rz / pap, x += a p, r -= a ap; z = minv .* r (not stored); then beta = z.r / rz,
+    rz = z.r and rr = r.r.  `scalars` is a DeviceVector holding rz, pap, beta, rr in its elements 0 .. 3, or a list
+    of four HBM addresses; it may be None (an error of the call)."""
+    if scalars is None:
+        sp = [None] * 4
+    elif isinstance(scalars, DeviceVector):
+        sp = [scalars.slot_ptr(k) for k in range(4)]
+    else:
+        sp = list(scalars)
+    rc = lib().spx_hip_vec_pcg_update(x.handle, p.handle, r.handle, ap.handle, minv.handle, sp[0], sp[1], sp[2], sp[3],
+                                      stream)
+    if rc != SPX_SUCCESS:
+        raise SpxError("spx_hip_vec_pcg_update failed (see stderr)")
+
+
+def pcg_direction(p, r, minv, scalars=None, stream=0):
+    """``spx_hip_vec_pcg_direction``: p <- minv .* r + beta p with beta = element 2 of the DeviceVector `scalars` (the
+    layout of pcg_update), or an HBM address; None: p <- minv .* r."""
+    if scalars is None:
+        bp = None
+    elif isinstance(scalars, DeviceVector):
+        bp = scalars.slot_ptr(2)
+    else:
+        bp = scalars
+    rc = lib().spx_hip_vec_pcg_direction(p.handle, r.handle, minv.handle, bp, stream)
+    if rc != SPX_SUCCESS:
+        raise SpxError("spx_hip_vec_pcg_direction failed (see stderr)")
 
 
 def mat_restore(filename):

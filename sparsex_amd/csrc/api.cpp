@@ -2650,6 +2650,120 @@ try {
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
+// ---- the diagonal of a tuned matrix ----------------------------------------------------------------------
+// The reference reads a tuned matrix entry by entry (spx_mat_get_entry, src/api/matvec.c:340-374).  A Jacobi
+// preconditioner wants the whole diagonal, in the numbering of the products' vectors and from the values as they
+// are now: one walk over the stream finds where every a(i, i) lies (diag_plan.cpp), one gather reads them
+// (csx_gather_diag_kernel, refresh_kernels.hip).
+
+static void diag_plan_forget(spx_matrix_t *A)
+{
+    if (A->dev) device_diag_plan_drop(A->dev);
+    A->diag_plan.reset();
+    A->diag_plan_bytes = 0;
+}
+
+spx_error_t spx_hip_mat_diag_plan(spx_matrix_t *A)
+try {
+    if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
+    const GpuStream *s = A->host_stream ? A->host_stream.get() : A->index.get();
+    if (!s) { SETERROR_1(SPX_ERR_TUNED_MAT, "matrix holds no descriptor stream"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    try {
+        DiagPlanInput in;
+        in.stream = s;
+        in.n_values = A->host_stream ? A->host_stream->values.size() : device_n_values(A->dev);
+        in.nrows = (size_t) A->nrows;
+        in.ncols = (size_t) A->ncols;
+        in.symmetric = A->symmetric != 0;
+        in.own_lo = (size_t) A->own_lo;
+        in.own_hi = (size_t) A->own_hi;
+        std::unique_ptr<DiagPlan> plan(new DiagPlan);
+        build_diag_plan(in, *plan, host_threads());
+        size_t bytes = 0;
+        if (A->dev) bytes = device_diag_plan_set(A->dev, *plan);
+        A->diag_plan = std::move(plan);
+        A->diag_plan_bytes = bytes;
+    } catch (const FatalError &e) {
+        // (no plan is left behind, an earlier one included)
+        diag_plan_forget(A);
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    } catch (const std::exception &e) {
+        diag_plan_forget(A);
+        SETERROR_1(SPX_ERR_MEM_ALLOC, e.what());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_diag_plan_drop(spx_matrix_t *A)
+try {
+    if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    diag_plan_forget(A);
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+static const char *const NO_DIAG_PLAN = "no diagonal plan: call spx_hip_mat_diag_plan first (a symmetric matrix needs none)";
+
+spx_error_t spx_hip_mat_get_diag(const spx_matrix_t *A, spx_value_t *d_dev, void *stream)
+try {
+    if (!A || !d_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    if (!A->dev) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "matrix was tuned with spx.rt.host_only=true: no HIP executor "
+                   "(spx_hip_mat_get_diag_host reads the host copy)");
+        return SPX_FAILURE;
+    }
+    if (!A->symmetric && !A->diag_plan) { SETERROR_1(SPX_ERR_TUNED_MAT, NO_DIAG_PLAN); return SPX_FAILURE; }
+    try {
+        device_get_diag(A->dev, d_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_get_diag_host(const spx_matrix_t *A_, spx_value_t *d)
+try {
+    spx_matrix_t *A = const_cast<spx_matrix_t *>(A_);
+    if (!A || !d) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    if (!A->symmetric && !A->diag_plan) { SETERROR_1(SPX_ERR_TUNED_MAT, NO_DIAG_PLAN); return SPX_FAILURE; }
+    try {
+        if (A->host_stream) {
+            DiagPlan own;
+            own.symmetric = true;
+            own.own_lo = (size_t) A->own_lo;
+            own.n_rows = (size_t) (A->own_hi - A->own_lo);
+            read_diag_host(A->symmetric ? own : *A->diag_plan, *A->host_stream, d);
+        } else if (A->dev) {
+            device_get_diag_host(A->dev, d);
+        } else {
+            throw FatalError("matrix holds no descriptor stream");
+        }
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_diag_plan_get(const spx_matrix_t *A, spx_hip_diag_plan_t *out)
+try {
+    if (!A || !out) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    if (!A->diag_plan) { SETERROR_1(SPX_ERR_TUNED_MAT, NO_DIAG_PLAN); return SPX_FAILURE; }
+    const DiagPlan &p = *A->diag_plan;
+    memset(out, 0, sizeof(*out));
+    out->pos = p.pos.empty() ? NULL : p.pos.data();
+    out->n_rows = p.n_rows;
+    out->row_lo = p.own_lo;
+    out->n_present = p.n_present;
+    out->plan_bytes = A->diag_plan_bytes;
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
 spx_error_t spx_hip_mat_info_sized(const spx_matrix_t *A, void *info, size_t size)
 try {
     spx_hip_info_t full;

@@ -169,6 +169,18 @@ size_t device_values_plan_set(DeviceMatrix *m, const ValuesPlan &plan);
 void device_values_plan_drop(DeviceMatrix *m);
 void device_set_values(DeviceMatrix *m, const double *d_csr_values, void *stream);
 void device_set_values_host(DeviceMatrix *m, const double *h_csr_values, size_t csr_nnz);
+// The diagonal (diag_plan.hpp).  device_diag_plan_set uploads the positions of a general stream's diagonal entries
+// (replacing an earlier plan; a symmetric stream has nothing to upload) and returns the HBM they take, on the
+// matrix' device, the current device left as it was.  device_get_diag enqueues ONE gather kernel on `stream` that
+// writes d_diag[own_lo, own_hi) -- no allocation, no wait, legal during stream capture; it counts as a product
+// for device_poke's wait-once rule.  device_get_diag_host: the same through a temporary HBM buffer, synchronous,
+// into host memory.  Both readers refuse a calling thread whose current device is not the matrix' one, and a
+// general stream without a plan.
+struct DiagPlan;
+size_t device_diag_plan_set(DeviceMatrix *m, const DiagPlan &plan);
+void device_diag_plan_drop(DeviceMatrix *m);
+void device_get_diag(DeviceMatrix *m, double *d_diag, void *stream);
+void device_get_diag_host(DeviceMatrix *m, double *h_diag);
 size_t device_n_values(const DeviceMatrix *m);     // doubles in the stream's value array
 
 struct DeviceMatrixInfo {

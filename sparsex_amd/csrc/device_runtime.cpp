@@ -11,6 +11,7 @@
 #include "sxplan.hpp"
 #include "threads.hpp"
 #include "values_plan.hpp"
+#include "diag_plan.hpp"
 #include "xwindows.hpp"
 
 #include <hip/hip_runtime_api.h>
@@ -163,6 +164,10 @@ struct DeviceMatrix {
     // device_build_values_f32): element i is
     // values[i] rounded to nearest, tail slack included; an allocation of its own, also next to an arena
     float *values_f32 = nullptr;
+    // where the diagonal lies (diag_plan.hpp; general streams): per own row the position in `values` or 0xffffffff
+    uint32_t *diag_pos = nullptr;
+    size_t diag_n = 0;
+    bool has_diag_plan = false;
 };
 
 // elements behind the end of the stream's values that the pipelined kernels' paired loads may touch (never used)
@@ -629,6 +634,7 @@ void device_free(DeviceMatrix *m)
         if (m->mirror_val) (void) hipFree(m->mirror_val);
     }
     device_values_plan_drop(m);
+    device_diag_plan_drop(m);
     if (m->values_f32) (void) hipFree(m->values_f32);
     if (m->passes_sx) (void) hipFree(m->passes_sx);
     if (m->sx_tab) (void) hipFree(m->sx_tab);
@@ -1782,6 +1788,96 @@ void device_set_values_host(DeviceMatrix *m, const double *h_csr_values, size_t 
         throw;
     }
     release();
+}
+
+// ---- the diagonal ----------------------------------------------------------------------------------------
+void device_diag_plan_drop(DeviceMatrix *m)
+{
+    if (m->diag_pos) (void) hipFree(m->diag_pos);
+    m->diag_pos = nullptr;
+    m->diag_n = 0;
+    m->has_diag_plan = false;
+}
+
+size_t device_diag_plan_set(DeviceMatrix *m, const DiagPlan &plan)
+{
+    if (plan.symmetric != m->symmetric || plan.own_lo != m->own_lo || plan.n_rows != m->own_hi - m->own_lo ||
+        (!plan.symmetric && plan.pos.size() != plan.n_rows))
+        throw FatalError("diagonal plan: not the plan of this stream");
+    for (uint32_t p : plan.pos)
+        if (p != DIAG_PLAN_NONE && p >= m->n_values) throw FatalError("diagonal plan: not the plan of this stream");
+    // (on the matrix' device, and the caller's current device as it was afterwards)
+    int before = -1;
+    HIP_CHECK(hipGetDevice(&before));
+    struct Back {
+        int dev;
+        ~Back() { (void) hipSetDevice(dev); }
+    } back{before};
+    HIP_CHECK(hipSetDevice(m->device));
+    device_diag_plan_drop(m);
+    size_t bytes = 0;
+    if (!plan.pos.empty()) {
+        bytes = plan.pos.size() * sizeof(uint32_t);
+        try {
+            HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&m->diag_pos), bytes));
+            HIP_CHECK(hipMemcpy(m->diag_pos, plan.pos.data(), bytes, hipMemcpyHostToDevice));
+        } catch (...) {
+            device_diag_plan_drop(m);
+            throw;
+        }
+    }
+    m->diag_n = plan.pos.size();
+    m->has_diag_plan = true;
+    return bytes;
+}
+
+// the own rows' diagonal to own[0, own_hi - own_lo)
+static void enqueue_own_diag(DeviceMatrix *m, double *own, void *stream)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+    const size_t n = m->own_hi - m->own_lo;
+    if (m->symmetric) {
+        if (!m->dvalues) throw FatalError("the symmetric stream holds no diagonal array");
+        m->launched_since_edit = true;
+        launch_gather_diag(stream, own, nullptr, m->dvalues + m->own_lo, n);
+        return;
+    }
+    if (!m->has_diag_plan || m->diag_n != n) throw FatalError("no diagonal plan: call spx_hip_mat_diag_plan first");
+    m->launched_since_edit = true;
+    launch_gather_diag(stream, own, m->diag_pos, m->values, n);
+}
+
+void device_get_diag(DeviceMatrix *m, double *d_diag, void *stream) { enqueue_own_diag(m, d_diag + m->own_lo, stream); }
+
+void device_get_diag_host(DeviceMatrix *m, double *h_diag)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+    const size_t n = m->own_hi - m->own_lo;
+    if (!n) return;
+    if (!m->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking));
+    hipStream_t st = m->host_stream;
+    double *d = nullptr;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), n * sizeof(double)));
+    try {
+        // (values a client's streams are still writing -- spx_hip_mat_set_values -- are not ordered against this
+        // stream: wait for them as device_poke does, once)
+        quiesce_before_edit(m);
+        enqueue_own_diag(m, d, st);
+        HIP_CHECK(hipMemcpyAsync(h_diag + m->own_lo, d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        m->launched_since_edit = false;
+    } catch (...) {
+        (void) hipStreamSynchronize(st);
+        (void) hipFree(d);
+        throw;
+    }
+    (void) hipFree(d);
 }
 
 size_t device_n_values(const DeviceMatrix *m) { return m->n_values; }

@@ -12,6 +12,7 @@
 #include "xwindows.hpp"
 #include "sxplan.hpp"
 #include "values_plan.hpp"
+#include "diag_plan.hpp"
 
 #include <algorithm>
 #include <functional>
@@ -120,6 +121,9 @@ struct matrix {
     std::unique_ptr<spx::ValuesPlan> values_plan;
     size_t values_plan_bytes = 0;
     bool values_refreshed = false;
+    // where the diagonal lies (spx_hip_mat_diag_plan, diag_plan.hpp): the host copy of the plan and the HBM its copy takes
+    std::unique_ptr<spx::DiagPlan> diag_plan;
+    size_t diag_plan_bytes = 0;
     // host-only matrices: the digest of the values held before the first bulk update (values_plan_digest), and
     // whether a spx_mat_set_entry has come since -- it leaves stale partitions alone, so they cannot become true again
     spx::ValuesDigest pre_refresh_digest;

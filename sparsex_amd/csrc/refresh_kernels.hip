@@ -75,7 +75,74 @@ csx_narrow_values_kernel(float4 *__restrict__ dst, const double2 *__restrict__ s
     dst[q] = make_float4(__double2float_rn(a.x), __double2float_rn(a.y), __double2float_rn(b.x), __double2float_rn(b.y));
 }
 
+// The way back for the diagonal (diag_plan.hpp): dst[i] = pos[i] != none ? values[pos[i]] : +0.0 for the n own
+// rows of a general stream; PLAN false: dst[i] = values[i], the diagonal array of a symmetric one.  The sibling of
+// csx_refresh_values_kernel: a lane takes four consecutive rows, one 16-byte load of the plan (it comes from
+// hipMalloc; NOT padded: the last group loads its entries one by one), four 8-byte gathers -- the diagonal
+// entries of neighbouring rows mostly lie in the same row-block -- and two 16-byte stores.  `dst` is a caller's
+// pointer plus the slice's first row and may be only 8-byte aligned: its groups store value by value (!ALIGNED),
+// as does the last group of an n that is no multiple of four.  Nothing outside [dst, dst + n) is written.
+template <bool ALIGNED, bool PLAN>
+__global__ void __launch_bounds__(REFRESH_BLOCK)
+csx_gather_diag_kernel(double *__restrict__ dst, const uint32_t *__restrict__ pos, const double *__restrict__ values,
+                       size_t n)
+{
+    const size_t q = (size_t) blockIdx.x * REFRESH_BLOCK + threadIdx.x;
+    const size_t i = q * 4;
+    if (i >= n) return;
+    if (i + 4 <= n) {
+        double v[4];
+        if (PLAN) {
+            const uint4 m = *reinterpret_cast<const uint4 *>(pos + i);
+            v[0] = m.x != REFRESH_NONE ? values[m.x] : 0.0;
+            v[1] = m.y != REFRESH_NONE ? values[m.y] : 0.0;
+            v[2] = m.z != REFRESH_NONE ? values[m.z] : 0.0;
+            v[3] = m.w != REFRESH_NONE ? values[m.w] : 0.0;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = values[i + k];
+        }
+        if (ALIGNED) {
+            double2 *out = reinterpret_cast<double2 *>(dst + i);
+            out[0] = make_double2(v[0], v[1]);
+            out[1] = make_double2(v[2], v[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) dst[i + k] = v[k];
+        }
+        return;
+    }
+    for (size_t k = i; k < n; ++k) {
+        if (PLAN) {
+            const uint32_t m = pos[k];
+            dst[k] = m != REFRESH_NONE ? values[m] : 0.0;
+        } else {
+            dst[k] = values[k];
+        }
+    }
+}
+
 }  // namespace
+
+void launch_gather_diag(void *stream, double *dst, const uint32_t *pos, const double *values, size_t n)
+{
+    if (!n) return;
+    const size_t n_quads = (n + 3) / 4;
+    const size_t blocks = (n_quads + REFRESH_BLOCK - 1) / REFRESH_BLOCK;
+    if (blocks > 0x7fffffffull) throw FatalError("diagonal: array too long for one launch");
+    if (pos && (reinterpret_cast<uintptr_t>(pos) & 15u) != 0) throw FatalError("diagonal: the plan must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool aligned = (reinterpret_cast<uintptr_t>(dst) & 15u) == 0;
+    const dim3 grid((unsigned) blocks), block(REFRESH_BLOCK);
+    if (pos) {
+        if (aligned) hipLaunchKernelGGL((csx_gather_diag_kernel<true, true>), grid, block, 0, st, dst, pos, values, n);
+        else hipLaunchKernelGGL((csx_gather_diag_kernel<false, true>), grid, block, 0, st, dst, pos, values, n);
+    } else {
+        if (aligned) hipLaunchKernelGGL((csx_gather_diag_kernel<true, false>), grid, block, 0, st, dst, pos, values, n);
+        else hipLaunchKernelGGL((csx_gather_diag_kernel<false, false>), grid, block, 0, st, dst, pos, values, n);
+    }
+    HIP_CHECK(hipGetLastError());
+}
 
 void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n, float *dst_f32)
 {

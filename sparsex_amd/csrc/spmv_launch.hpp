@@ -154,6 +154,10 @@ void spmv_mvsym_allow_lds(size_t bytes);
 // (both 16-byte aligned then).
 void launch_refresh_values(void *stream, double *dst, const uint32_t *map, const double *src, size_t n,
                            float *dst_f32 = nullptr);
+// the diagonal of a tuned matrix (diag_plan.hpp): dst[i] = values[pos[i]], +0.0 where pos[i] is 0xffffffff, for
+// i < n; pos == null: dst[i] = values[i] (the diagonal array of a symmetric stream).  `pos` is 16-byte aligned
+// and holds n entries, `dst` any 8-byte aligned address.  Enqueues on `stream`, nothing else.
+void launch_gather_diag(void *stream, double *dst, const uint32_t *pos, const double *values, size_t n);
 // dst[i] = (float) src[i] for i < n, round to nearest even; n a multiple of four, both arrays 16-byte aligned
 void launch_narrow_values(void *stream, float *dst, const double *src, size_t n);
 

@@ -1,7 +1,7 @@
 // values_plan.cpp -- see values_plan.hpp.
 #include "values_plan.hpp"
 
-#include "stream_lanes.hpp"
+#include "stream_walk.hpp"
 #include "threads.hpp"
 
 #include <algorithm>
@@ -182,38 +182,8 @@ void build_values_plan(const ValuesPlanInput &in, ValuesPlan &plan, unsigned nth
         dst[pos] = k;
         count_hit(hits, k);
     };
-    constexpr size_t RB_CHUNK = 16;
-    const size_t n_rb = s.rbs.size();
-    parallel_for((n_rb + RB_CHUNK - 1) / RB_CHUNK, nthreads, [&](size_t c) {
-        for (size_t i = c * RB_CHUNK; i < std::min(n_rb, (c + 1) * RB_CHUNK); ++i) {
-            const SpxRowBlock &rb = s.rbs[i];
-            for (uint32_t t = 0; t < rb.n_pass; ++t) {
-                const SpxPass &ps = s.passes[(size_t) rb.pass_off + t];
-                const uint32_t nseg = ps.nseg, W = ps.width;
-                const size_t vbase = (size_t) rb.val_off + ps.val_off;
-                for (uint32_t l = 0; l < nseg; ++l) {
-                    if (is_gather(ps)) {
-                        // (lanes beyond a piece's length are padding)
-                        const uint32_t sr = s.segrows[(size_t) rb.seg_off + ps.seg0 + l];
-                        const int64_t row = (int64_t) rb.row0 + SPX_SEGROW_ROW(sr);
-                        for (uint32_t w = 0; w < W && w < SPX_SEGROW_LEN(sr); ++w)
-                            place(plan.src_values, vbase + spx_pass_value_index(l, w, nseg, W), row,
-                                  gather_col(s, rb, ps, (size_t) ps.elem0 + l + (size_t) w * nseg), false);
-                    } else if (ps.kind == SPX_PASS_SYMTILE) {
-                        // (a cell of a tile that the matrix does not hold stays the zero the tune put there)
-                        int64_t r, c0;
-                        tile_lane(s, rb, ps, l, r, c0);
-                        for (uint32_t w = 0; w < 8; ++w)
-                            place(plan.src_values, vbase + spx_pass_value_index(l, w, nseg, 8), (int64_t) rb.row0 + r, c0 + w, true);
-                    } else {
-                        int64_t r, c0;
-                        unit_lane(s, rb, ps, l, r, c0);
-                        for (uint32_t w = 0; w < W; ++w)
-                            place(plan.src_values, vbase + spx_pass_value_index(l, w, nseg, W), (int64_t) rb.row0 + r, c0 + w, false);
-                    }
-                }
-            }
-        }
+    for_each_stored_value(s, nthreads, [&](size_t pos, int64_t trow, int64_t tcol, bool may_be_absent) {
+        place(plan.src_values, pos, trow, tcol, may_be_absent);
     });
     // ... the thin mirror list of a symmetric slice: entry k of row t is the mirror image of (column, row)
     for (size_t t = 0; t < s.mirror_rows.size(); ++t)

@@ -72,13 +72,27 @@ __device__ __forceinline__ bool vec_chunk(size_t n2, size_t nchunks, size_t per,
     return lo < hi;
 }
 
-// kind: 0 init (d = s), 1 scale (d = s*a), 2 axpy (d = a + s*b), 3 copy (d = a)
+// a * b rounded once, whatever follows: a product that -ffp-contract must not fold into a sum behind it (the
+// toolchain's __dmul_rn is a plain `a * b`, which it folds)
+__device__ __forceinline__ double mul_rn(double a, double b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+// 1 / a, or s where a is +-0: one IEEE division
+__device__ __forceinline__ double recip_or(double a, double s) { return a == 0.0 ? s : 1.0 / a; }
+
+// kind: 0 init (d = s), 1 scale (d = s*a), 2 axpy (d = a + s*b), 3 copy (d = a), 4 product (d = a .* b),
+// 5 reciprocal (d = 1 / a, s where a is +-0)
 template <int KIND>
 __device__ __forceinline__ double2 vec_map_one(double2 va, double2 vb, double s)
 {
     if (KIND == 0) return make_double2(s, s);
     if (KIND == 1) return make_double2(s * va.x, s * va.y);
     if (KIND == 3) return va;
+    if (KIND == 4) return make_double2(mul_rn(va.x, vb.x), mul_rn(va.y, vb.y));
+    if (KIND == 5) return make_double2(recip_or(va.x, s), recip_or(va.y, s));
     return make_double2(va.x + s * vb.x, va.y + s * vb.y);
 }
 
@@ -89,7 +103,8 @@ __device__ __forceinline__ void vec_map_chunk(double *__restrict__ d, const doub
 {
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const size_t i = n - 1;
-        d[i] = KIND == 0 ? s : KIND == 1 ? s * a[i] : KIND == 3 ? a[i] : a[i] + s * b[i];
+        d[i] = KIND == 0 ? s : KIND == 1 ? s * a[i] : KIND == 3 ? a[i] : KIND == 4 ? mul_rn(a[i], b[i]) :
+               KIND == 5 ? recip_or(a[i], s) : a[i] + s * b[i];
     }
     size_t lo, hi;
     if (!vec_chunk(n / 2, nchunks, per, chunk_len, lo, hi)) return;
@@ -102,14 +117,14 @@ __device__ __forceinline__ void vec_map_chunk(double *__restrict__ d, const doub
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             va[k] = KIND == 0 ? make_double2(0.0, 0.0) : a2[i + k * VEC_BLOCK];
-            vb[k] = KIND == 2 ? b2[i + k * VEC_BLOCK] : make_double2(0.0, 0.0);
+            vb[k] = KIND == 2 || KIND == 4 ? b2[i + k * VEC_BLOCK] : make_double2(0.0, 0.0);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) d2[i + k * VEC_BLOCK] = vec_map_one<KIND>(va[k], vb[k], s);
     }
     for (; i < hi; i += VEC_BLOCK) {
         const double2 va = KIND == 0 ? make_double2(0.0, 0.0) : a2[i];
-        const double2 vb = KIND == 2 ? b2[i] : make_double2(0.0, 0.0);
+        const double2 vb = KIND == 2 || KIND == 4 ? b2[i] : make_double2(0.0, 0.0);
         d2[i] = vec_map_one<KIND>(va, vb, s);
     }
 }
@@ -284,6 +299,125 @@ __global__ __launch_bounds__(VEC_BLOCK) void vec_cg_finish_kernel(const double *
         const double old = *rr;
         *beta = old == 0.0 ? 0.0 : t / old;
         *rr = t;
+    }
+}
+
+// One Jacobi-preconditioned CG update in one pass: vec_cg_update_kernel with a fifth stream in, the diagonal
+// preconditioner minv, and a second sum.  a = *rz / *pap (0 if *pap == 0); x += a p; r -= a ap -- the bits of
+// vec_cg_update_kernel for the same a; z = minv .* r in ONE rounded multiplication (mul_rn: -ffp-contract must
+// not fold it into the sum behind it) and never stored; the workgroup's share of r . r to partials[blockIdx.x] --
+// the grid, the order and so the bits of vec_cg_update_kernel -- and of z . r to partials[gridDim.x + blockIdx.x].
+__global__ __launch_bounds__(VEC_BLOCK) void vec_pcg_update_kernel(double *__restrict__ x, const double *__restrict__ p,
+                                                                   double *__restrict__ r, const double *__restrict__ ap,
+                                                                   const double *__restrict__ minv, const double *rz,
+                                                                   const double *pap, double *__restrict__ partials,
+                                                                   size_t n, size_t nchunks, size_t per, unsigned chunk_len)
+{
+    __shared__ double wsum_rr[VEC_BLOCK / 64], wsum_rz[VEC_BLOCK / 64];
+    const double a = dev_ratio(1.0, rz, pap), na = -a;
+    double acc = 0.0, accz = 0.0;
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const size_t i = n - 1;
+        x[i] = x[i] + a * p[i];
+        const double rn = r[i] + na * ap[i];
+        r[i] = rn;
+        acc = rn * rn;
+        accz = fma(mul_rn(minv[i], rn), rn, 0.0);
+    }
+    size_t lo, hi;
+    if (vec_chunk(n / 2, nchunks, per, chunk_len, lo, hi)) {
+        double2 *x2 = reinterpret_cast<double2 *>(x), *r2 = reinterpret_cast<double2 *>(r);
+        const double2 *p2 = reinterpret_cast<const double2 *>(p), *ap2 = reinterpret_cast<const double2 *>(ap);
+        const double2 *m2 = reinterpret_cast<const double2 *>(minv);
+        size_t i = lo + threadIdx.x;
+        for (; i + 3 * VEC_BLOCK < hi; i += 4 * VEC_BLOCK) {
+            double2 vx[4], vp[4], vr[4], vq[4], vm[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                vx[k] = x2[i + k * VEC_BLOCK];
+                vp[k] = p2[i + k * VEC_BLOCK];
+                vr[k] = r2[i + k * VEC_BLOCK];
+                vq[k] = ap2[i + k * VEC_BLOCK];
+                vm[k] = m2[i + k * VEC_BLOCK];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                x2[i + k * VEC_BLOCK] = vec_map_one<2>(vx[k], vp[k], a);
+                const double2 rn = vec_map_one<2>(vr[k], vq[k], na);
+                r2[i + k * VEC_BLOCK] = rn;
+                acc = fma(rn.x, rn.x, acc);
+                acc = fma(rn.y, rn.y, acc);
+                accz = fma(mul_rn(vm[k].x, rn.x), rn.x, accz);
+                accz = fma(mul_rn(vm[k].y, rn.y), rn.y, accz);
+            }
+        }
+        for (; i < hi; i += VEC_BLOCK) {
+            x2[i] = vec_map_one<2>(x2[i], p2[i], a);
+            const double2 rn = vec_map_one<2>(r2[i], ap2[i], na), vm = m2[i];
+            r2[i] = rn;
+            acc = fma(rn.x, rn.x, acc);
+            acc = fma(rn.y, rn.y, acc);
+            accz = fma(mul_rn(vm.x, rn.x), rn.x, accz);
+            accz = fma(mul_rn(vm.y, rn.y), rn.y, accz);
+        }
+    }
+    const double t = block_sum(acc, wsum_rr), tz = block_sum(accz, wsum_rz);
+    if (threadIdx.x == 0) {
+        partials[blockIdx.x] = t;                              // (a workgroup without a chunk: 0)
+        partials[gridDim.x + blockIdx.x] = tz;
+    }
+}
+
+// ... and its finish: both sums in workgroup order, *beta = new z . r / old (0 if old == 0), *rz = new, *rr = r . r
+__global__ __launch_bounds__(VEC_BLOCK) void vec_pcg_finish_kernel(const double *partials, unsigned nblocks, double *rz,
+                                                                   double *beta, double *rr)
+{
+    __shared__ double wsum_rr[VEC_BLOCK / 64], wsum_rz[VEC_BLOCK / 64];
+    const double t = partials_sum(partials, nblocks, wsum_rr), tz = partials_sum(partials + nblocks, nblocks, wsum_rz);
+    if (threadIdx.x == 0) {
+        const double old = *rz;
+        *beta = old == 0.0 ? 0.0 : tz / old;
+        *rz = tz;
+        *rr = t;
+    }
+}
+
+// p <- minv .* r + beta p, beta = *beta_dev; !HAS_BETA: p <- minv .* r.  The product as vec_map_kernel<4> rounds it,
+// the sum as vec_map_kernel<2> forms it from that z: the bits of the two calls, without the pass over z.
+template <bool HAS_BETA>
+__global__ __launch_bounds__(VEC_BLOCK) void vec_pcg_direction_kernel(double *__restrict__ p, const double *__restrict__ r,
+                                                                      const double *__restrict__ minv, const double *beta_dev,
+                                                                      size_t n, size_t nchunks, size_t per, unsigned chunk_len)
+{
+    const double beta = HAS_BETA ? *beta_dev : 0.0;
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const size_t i = n - 1;
+        const double z = mul_rn(minv[i], r[i]);
+        p[i] = HAS_BETA ? z + beta * p[i] : z;
+    }
+    size_t lo, hi;
+    if (!vec_chunk(n / 2, nchunks, per, chunk_len, lo, hi)) return;
+    const double2 *r2 = reinterpret_cast<const double2 *>(r), *m2 = reinterpret_cast<const double2 *>(minv);
+    double2 *p2 = reinterpret_cast<double2 *>(p);
+    const double2 none = make_double2(0.0, 0.0);
+    size_t i = lo + threadIdx.x;
+    for (; i + 3 * VEC_BLOCK < hi; i += 4 * VEC_BLOCK) {
+        double2 vr[4], vm[4], vp[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            vr[k] = r2[i + k * VEC_BLOCK];
+            vm[k] = m2[i + k * VEC_BLOCK];
+            vp[k] = HAS_BETA ? p2[i + k * VEC_BLOCK] : none;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double2 z = vec_map_one<4>(vm[k], vr[k], 0.0);
+            p2[i + k * VEC_BLOCK] = HAS_BETA ? vec_map_one<2>(z, vp[k], beta) : z;
+        }
+    }
+    for (; i < hi; i += VEC_BLOCK) {
+        const double2 z = vec_map_one<4>(m2[i], r2[i], 0.0);
+        p2[i] = HAS_BETA ? vec_map_one<2>(z, p2[i], beta) : z;
     }
 }
 
@@ -525,6 +659,94 @@ spx_error_t spx_hip_vec_cg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_
                        beta_dev);
     VEC_TRY(hipGetLastError());
     return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_vec_mul_elem(const spx_hip_vec_t *v1, const spx_hip_vec_t *v2, spx_hip_vec_t *v3, void *stream)
+{
+    if (same_size(v1, v2) != SPX_SUCCESS || same_size(v1, v3) != SPX_SUCCESS) return SPX_FAILURE;
+    return map<4>(v3, v1, v2, 0.0, stream);
+}
+
+spx_error_t spx_hip_vec_reciprocal(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, spx_value_t if_zero, void *stream)
+{
+    if (same_size(v1, v2) != SPX_SUCCESS) return SPX_FAILURE;
+    return map<5>(v2, v1, nullptr, if_zero, stream);
+}
+
+spx_error_t spx_hip_vec_pcg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_hip_vec_t *r, const spx_hip_vec_t *ap,
+                                   const spx_hip_vec_t *minv, spx_value_t *rz_dev, const spx_value_t *pap_dev,
+                                   spx_value_t *beta_dev, spx_value_t *rr_dev, void *stream_)
+{
+    if (same_size(x, p) != SPX_SUCCESS || same_size(x, r) != SPX_SUCCESS || same_size(x, ap) != SPX_SUCCESS ||
+        same_size(x, minv) != SPX_SUCCESS)
+        return SPX_FAILURE;
+    if (!rz_dev || !pap_dev || !beta_dev || !rr_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid device scalar"); return SPX_FAILURE; }
+    const spx_hip_vec_t *v[5] = {x, p, r, ap, minv};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (v[i] == v[j]) {
+                SETERROR_1(SPX_ERR_ARG_INVALID, "x, p, r, ap and minv must be five different vectors");
+                return SPX_FAILURE;
+            }
+    const spx_value_t *sc[4] = {rz_dev, pap_dev, beta_dev, rr_dev};
+    for (int i = 0; i < 4; ++i) {
+        for (int j = i + 1; j < 4; ++j)
+            if (sc[i] == sc[j]) {
+                SETERROR_1(SPX_ERR_ARG_INVALID, "rz, pap, beta and rr must be four different device scalars");
+                return SPX_FAILURE;
+            }
+        if (inside(sc[i], x) || inside(sc[i], r)) {
+            SETERROR_1(SPX_ERR_ARG_INVALID, "a device scalar lies inside a vector the call writes");
+            return SPX_FAILURE;
+        }
+    }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // (size 0: the grid of one empty chunk, so that rz, rr and beta are still written)
+    const VecGrid g = grid_for(x->size, VEC_CHUNK_CG);
+    // both arrays of partial sums in r's scratch: partials_for() is cut for the finest grid there is, twice as
+    // fine as this one at its finest
+    if (2 * (size_t) g.blocks > partials_for(r->size)) {
+        SETERROR_1(SPX_ERR_VEC, "the vector's scratch holds no room for two partial sums per workgroup");
+        return SPX_FAILURE;
+    }
+    hipLaunchKernelGGL(vec_pcg_update_kernel, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, x->data, p->data, r->data,
+                       ap->data, minv->data, rz_dev, pap_dev, r->partials, x->size, g.nchunks, g.per, g.chunk);
+    hipLaunchKernelGGL(vec_pcg_finish_kernel, dim3(1), dim3(VEC_BLOCK), 0, stream, r->partials, g.blocks, rz_dev,
+                       beta_dev, rr_dev);
+    VEC_TRY(hipGetLastError());
+    return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_vec_pcg_direction(spx_hip_vec_t *p, const spx_hip_vec_t *r, const spx_hip_vec_t *minv,
+                                      const spx_value_t *beta_dev, void *stream_)
+{
+    if (same_size(p, r) != SPX_SUCCESS || same_size(p, minv) != SPX_SUCCESS) return SPX_FAILURE;
+    if (p == r || p == minv || r == minv) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "p, r and minv must be three different vectors");
+        return SPX_FAILURE;
+    }
+    if (inside(beta_dev, p)) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "a device scalar lies inside the vector the call writes");
+        return SPX_FAILURE;
+    }
+    if (p->size == 0) return SPX_SUCCESS;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const VecGrid g = grid_for(p->size, VEC_CHUNK_MAP);
+    if (beta_dev)
+        hipLaunchKernelGGL(vec_pcg_direction_kernel<true>, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, p->data, r->data,
+                           minv->data, beta_dev, p->size, g.nchunks, g.per, g.chunk);
+    else
+        hipLaunchKernelGGL(vec_pcg_direction_kernel<false>, dim3(g.blocks), dim3(VEC_BLOCK), 0, stream, p->data, r->data,
+                           minv->data, beta_dev, p->size, g.nchunks, g.per, g.chunk);
+    VEC_TRY(hipGetLastError());
+    return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_mat_get_diag_vec(const spx_matrix_t *A, spx_hip_vec_t *d, void *stream)
+{
+    if (!A || !d) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid argument"); return SPX_FAILURE; }
+    if (d->size != (size_t) spx_mat_get_nrows(A)) { SETERROR_0(SPX_ERR_DIM); return SPX_FAILURE; }
+    return spx_hip_mat_get_diag(A, d->data, stream);
 }
 
 // ---- the roof of a read stream with a few stores in it (diagnostic) -------------------------------------
