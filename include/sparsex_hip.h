@@ -284,6 +284,38 @@ spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size
  * largest row-block's slots and y tile fit 80 KB of LDS (two workgroups per compute unit). */
 int spx_hip_matmat_group(const spx_matrix_t *A);
 
+/* ---- multi-vector product on row-major (interleaved) blocks ----------------------------
+ * Y <- alpha*A*X + beta*Y for nvec vectors at once, on device memory, for the layout a torch tensor of shape
+ * (ncols, nvec) or a PETSc-style dense block has: entry (i, j) of X is X_dev[i*ldx + j] (i < ncols, j < nvec,
+ * ldx >= nvec), entry (i, j) of Y is Y_dev[i*ldy + j] (i < nrows, j < nvec, ldy >= nvec).  HBM pointers on the
+ * matrix's device; the call only enqueues and allocates nothing (hipGraph-capturable), like
+ * spx_hip_matvec_kernel, refuses a thread whose current device is not the matrix', and the handle stays
+ * single-stream.
+ * Column j of Y is what spx_hip_matvec_kernel writes for column j of X (taken as a contiguous vector): on a row
+ * slice the same rows are written, beta == 0 never reads Y, and with spx.gpu.deterministic=true every column is
+ * bit-identical to that product.  The positions j >= nvec of a row (the padding up to ldx / ldy) are never
+ * multiplied and never written; nvec == 0 does nothing.  X and Y must not overlap.
+ * General (non-symmetric) tunes only.  A symmetric handle is refused with a message that says so: the
+ * single-vector kernels cannot read a strided x, so there is no per-column fallback (tune the matrix of a block
+ * solver as general, or hand spx_hip_matmat_kernel column-major blocks).  A matrix with an exchange plan attached
+ * (spx_hip_mat_dist_attach) is refused as well.
+ * SPX_FAILURE (through the error handler, nothing enqueued) for these two, a NULL handle, a host-only matrix, a
+ * NULL pointer with nvec > 0, ldx < nvec, ldy < nvec, overlapping X and Y, and the wrong current device.
+ * One pass over the matrix' stream serves spx_hip_matmat_rm_group(A) vectors; a remainder runs as groups of 4, 2
+ * and 1 (one vector of such a block is still strided: it has a kernel of its own).  A lane reads the nvec values of
+ * a column of A's row as one contiguous run -- 16 bytes per load where X_dev + j0 and ldx*8 are multiples of 16
+ * for the group's first vector j0, 8 bytes otherwise -- where the column-major product gathers one value per
+ * vector.
+ */
+spx_error_t spx_hip_matmat_rm_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                     const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                     spx_value_t *Y_dev, size_t ldy, void *stream);
+/* Diagnostic: how many vectors one pass of spx_hip_matmat_rm_kernel over this matrix' stream serves: the widest
+ * of 8, 4, 2, 1 of which that many y tiles of the largest row-block (per wavefront where the tune keeps a tile
+ * per wavefront) fit 80 KB of LDS -- the rule of spx_hip_matmat_group.  0: a symmetric handle, which the
+ * product refuses; -1: a matrix without a device copy. */
+int spx_hip_matmat_rm_group(const spx_matrix_t *A);
+
 /* ---- device-resident vectors ---------------------------------------------------
  * HBM counterparts of the reference's host vector helpers (spx_vec_init,
  * spx_vec_scale, spx_vec_scale_add, spx_vec_add, spx_vec_sub, spx_vec_mul,

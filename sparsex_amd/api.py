@@ -438,6 +438,62 @@ class Matrix:
         self.hip_matmat_kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
         return Y
 
+    def hip_matmat_rm_kernel(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
+        """``spx_hip_matmat_rm_kernel``: Y <- alpha*A*X + beta*Y for nvec vectors of row-major (interleaved)
+        blocks in HBM (entry (i, j) of X at x_ptr + 8*(i*ldx + j), of Y at y_ptr + 8*(i*ldy + j)).  General
+        tunes only."""
+        L = lib()
+        L.spx_hip_matmat_rm_kernel.restype = C.c_int
+        L.spx_hip_matmat_rm_kernel.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+        rc = L.spx_hip_matmat_rm_kernel(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
+        if rc != SPX_SUCCESS:
+            raise SpxError("spx_hip_matmat_rm_kernel failed (see stderr)")
+
+    def matmat_rm_group(self):
+        """``spx_hip_matmat_rm_group``: vectors one pass of the row-major product serves (8, 4, 2 or 1;
+        0: a symmetric handle, which it refuses; -1: no device copy)."""
+        L = lib()
+        L.spx_hip_matmat_rm_group.restype = C.c_int
+        L.spx_hip_matmat_rm_group.argtypes = [C.c_void_p]
+        return int(L.spx_hip_matmat_rm_group(C.c_void_p(self.handle)))
+
+    def matmat_rm(self, alpha, X, beta, Y, stream=None):
+        """Y <- alpha*A*X + beta*Y for torch float64 tensors on the matrix' device in the layout of ``A @ X``:
+        X of shape (ncols, nvec), Y of shape (nrows, nvec), each column one vector, stride(1) == 1 and
+        stride(0) >= nvec the leading dimension.  General tunes only.  `stream`: a torch stream (default: the
+        current one of Y's device).  Returns Y."""
+        import torch
+        pairs = (("X", X, self.ncols), ("Y", Y, self.nrows))
+        for name, t, n in pairs:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a torch tensor" % name)
+            if t.dtype != torch.float64:
+                raise ValueError("%s must be float64, not %s" % (name, t.dtype))
+            if t.dim() != 2 or t.shape[0] != n:
+                raise ValueError("%s must have the shape (%d, nvec), not %s" % (name, n, tuple(t.shape)))
+        if X.shape[1] != Y.shape[1]:
+            raise ValueError("X holds %d vectors, Y %d" % (X.shape[1], Y.shape[1]))
+        for name, t, n in pairs:
+            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s needs stride(1) == 1, not %d" % (name, t.stride(1)))
+            if t.shape[0] > 1 and t.shape[1] > 0 and t.stride(0) < t.shape[1]:
+                raise ValueError("%s: stride(0) %d is below the number of vectors %d" % (name, t.stride(0), t.shape[1]))
+        for name, t, n in pairs:
+            if t.device.type != "cuda":
+                raise ValueError("%s must live on the matrix' HIP device, not on %s" % (name, t.device))
+        if X.device != Y.device:
+            raise ValueError("X and Y live on different devices (%s, %s)" % (X.device, Y.device))
+        inf = self.info()
+        if inf.on_device and X.device.index != inf.device:
+            raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, X.device))
+        nvec = int(X.shape[1])
+        ldx = max(int(X.stride(0)), nvec) if self.ncols > 1 else max(nvec, 1)
+        ldy = max(int(Y.stride(0)), nvec) if self.nrows > 1 else max(nvec, 1)
+        st = stream if stream is not None else torch.cuda.current_stream(Y.device)
+        self.hip_matmat_rm_kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
+        return Y
+
     def info(self):
         inf = HipInfo()
         if lib().spx_hip_mat_info(self.handle, C.byref(inf)) != SPX_SUCCESS:

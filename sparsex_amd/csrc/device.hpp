@@ -61,6 +61,14 @@ void device_spmm(DeviceMatrix *m, double alpha, const double *d_X, size_t ldx, s
 // vectors per pass over the stream: 2, 4 or 8, or 1 (streams with symmetric tiles or read-once segments: one
 // single-vector product per column)
 int device_mv_group(const DeviceMatrix *m);
+// ... for nvec vectors of ROW-MAJOR blocks (entry (i, j) of X at d_X + i * ldx + j, of Y at d_Y + i * ldy + j);
+// column j is what device_spmv writes for column j of X.  General streams only (FatalError otherwise: the
+// single-vector kernels cannot read a strided x); groups of device_mv_group_rm(m) vectors, then 4 / 2 / 1, share
+// one pass over the stream (spmv_mvr_kernels.hip); asynchronous on `stream`, no allocation.
+void device_spmm_rm(DeviceMatrix *m, double alpha, const double *d_X, size_t ldx, size_t nvec, double beta,
+                    double *d_Y, size_t ldy, void *stream);
+// vectors per pass of that product: 8, 4, 2 or 1; 0: a stream it does not serve (symmetric)
+int device_mv_group_rm(const DeviceMatrix *m);
 
 // The product in K launches over consecutive parts of the row-blocks (equal work each), so that
 // the exchange of a row-partitioned matrix can start on the rows of part k while part k + 1 is

@@ -320,6 +320,7 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
         }
         place.put(&m->carry_mv, no_doubles, (size_t) MV_MAX_GROUP * (s.n_carry ? s.n_carry : 1));
         spmv_mv_allow_lds(160u * 1024u);
+        if (!symmetric) spmv_mvr_allow_lds(160u * 1024u);
     } else if (symmetric && s.sym_matmat) {
         // (read-once passes for K vectors: device_mv_group decides from what the stream and its settings allow)
         m->sym_matmat = true;
@@ -661,7 +662,7 @@ struct SpmvPart {
     bool first, last;
 };
 static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
-                           size_t ldy, void *stream_, const SpmvPart *part, bool f32 = false);
+                           size_t ldy, void *stream_, const SpmvPart *part, bool f32 = false, bool rm = false);
 
 void device_spmv(DeviceMatrix *m, double alpha, const double *d_x, double beta,
                  double *d_y, void *stream_)
@@ -910,9 +911,10 @@ int device_mv_group(const DeviceMatrix *m)
 
 static uint32_t mv_n_carry(const DeviceMatrix *m) { return m->n_carry ? m->n_carry : 1u; }
 
-// launch_rowblocks for K >= 2 vectors: the plain stream through the kernels of spmv_mv_kernels.hip
+// launch_rowblocks for K >= 2 vectors: the plain stream through the kernels of spmv_mv_kernels.hip; `rm`: for K >= 1
+// vectors of row-major blocks (general streams only: device_spmm_rm) through those of spmv_mvr_kernels.hip
 static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &a, size_t ldx, size_t ldy,
-                                const XcdSplit &xcd_now, uint32_t blocks, void *stream)
+                                const XcdSplit &xcd_now, uint32_t blocks, void *stream, bool rm)
 {
     if (!blocks) return;
     MvArgs mv{};
@@ -920,6 +922,17 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
     mv.x = a.x; mv.y = a.y; mv.ldx = ldx; mv.ldy = ldy;
     mv.carry = m->carry_mv; mv.n_carry = mv_n_carry(m);
     mv.dvalues = a.dvalues; mv.alpha = a.alpha; mv.beta = a.beta; mv.pass_stride = a.pass_stride;
+    if (rm) {
+        // the same families, LDS formula and staging rule as the column-major launch below; 16-byte loads of x
+        // where every column's K doubles are 16-byte aligned
+        MvrArgs mr{};
+        static_cast<MvArgs &>(mr) = mv;
+        mr.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
+        mr.x16 = ((uintptr_t) a.x % 16u == 0 && (ldx * sizeof(double)) % 16u == 0) ? 1u : 0u;
+        const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
+        launch_spmv_mvr(family, K, m->waves, blocks, mv_lds_bytes(m, K, mr.stage != 0), stream, mr, xcd_now);
+        return;
+    }
     if (m->has_tiles) {
         // read-once passes (device_mv_group: mvsym_on): the K x windows behind the K x {slots, y tile} where they fit
         MvSymArgs ms{};
@@ -940,8 +953,10 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
 // sequence of launches: init or scale, the row-blocks of every column phase, fix-up.  K == 1 runs the kernel that
 // the stream and the matrix' settings call for (launch_rowblocks), K = 2, 4, 8 (device_mv_group: streams without
 // symmetric tiles or read-once segments, or with spx.gpu.sym_matmat) the K-vector kernels over the plain stream.
+// `rm` (general streams, K = 1, 2, 4, 8): X and Y are row-major, entry (i, j) at X[i * ldx + j] and Y[i * ldy + j]; the
+// same sequence with the interleaved forms of the scale, row-block and fix-up kernels (spmv_mvr_kernels.hip).
 static void device_product(DeviceMatrix *m, int K, double alpha, const double *X, size_t ldx, double beta, double *Y,
-                           size_t ldy, void *stream_, const SpmvPart *part, bool f32)
+                           size_t ldy, void *stream_, const SpmvPart *part, bool f32, bool rm)
 {
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
@@ -988,7 +1003,7 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
     if (m->accum && !m->symmetric) {
         // column slices in one launch: beta * y first, every row-block adds on top
         const size_t lo = m->own_lo, hi = m->own_hi;
-        if (hi > lo) launch_scale(stream_, K, Y, ldy, lo, hi, beta);
+        if (hi > lo) (rm ? launch_scale_rm : launch_scale)(stream_, K, Y, ldy, lo, hi, beta);
         a.beta = beta = 1.0;
     }
     bool need_symfix = false;
@@ -997,14 +1012,16 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
         if (ph > 0) a.beta = 1.0;
         const XcdSplit &split = part ? part->split : m->xcd_split[ph];
         const uint32_t blocks = 8u * (part ? part->longest : m->xcd_longest[ph]);
-        if (K == 1) need_symfix |= launch_rowblocks(m, a, split, blocks, stream_, f32);
-        else launch_rowblocks_mv(m, K, a, ldx, ldy, split, blocks, stream_);
+        if (K == 1 && !rm) need_symfix |= launch_rowblocks(m, a, split, blocks, stream_, f32);
+        else launch_rowblocks_mv(m, K, a, ldx, ldy, split, blocks, stream_, rm);
     }
     if (part && !part->last) {
         HIP_CHECK(hipGetLastError());
         return;
     }
-    if (m->n_shared)
+    if (m->n_shared && rm)
+        launch_fixup_rm(stream_, K, m->shared, m->n_shared, m->carry_mv, mv_n_carry(m), Y, ldy, alpha, beta);
+    else if (m->n_shared)
         launch_fixup(stream_, K, m->shared, m->n_shared, K == 1 ? m->carry : m->carry_mv, mv_n_carry(m), Y, ldy, alpha,
                      beta, a.dvalues, X, ldx, f32);
     // the spilled column sums are added last: a row that is split over several row-blocks gets its
@@ -1024,6 +1041,33 @@ void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, siz
         int K = G;
         while (K > 1 && (size_t) K > nvec - j) K /= 2;
         device_product(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_, nullptr);
+        j += (size_t) K;
+    }
+}
+
+// the widest group of the row-major product: the budget and the formula of device_mv_group for general streams
+// (mv_lds_bytes: K y tiles per copy), 1 where only the one-vector instance fits; 0: a stream this product does not
+// serve (symmetric, or without the K-wide carry)
+int device_mv_group_rm(const DeviceMatrix *m)
+{
+    if (m->symmetric || m->has_tiles || !m->carry_mv) return 0;
+    for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
+        if (mv_lds_bytes(m, K, false) <= MV_LDS_BUDGET) return K;
+    return 1;
+}
+
+// Y <- alpha*A*X + beta*Y for nvec vectors of row-major blocks (entry (i, j) of X at X[i * ldx + j], of Y at
+// Y[i * ldy + j]): groups of the widest K that fits, then 4 / 2 / 1 for the remainder, group j0 on X + j0, Y + j0.
+// General streams only: the single-vector kernels cannot read a strided x, so there is no per-column fallback.
+void device_spmm_rm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
+                    size_t ldy, void *stream_)
+{
+    const int G = device_mv_group_rm(m);
+    if (G < 1) throw FatalError("the row-major multi-vector product serves general (non-symmetric) tunes only");
+    for (size_t j = 0; j < nvec;) {
+        int K = G;
+        while (K > 1 && (size_t) K > nvec - j) K /= 2;
+        device_product(m, K, alpha, X + j, ldx, beta, Y + j, ldy, stream_, nullptr, false, true);
         j += (size_t) K;
     }
 }

@@ -1,7 +1,7 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the six interpreter translation
+// XCD-aware row-block order, the kernel families and the launchers of the seven interpreter translation
 // units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_t_kernels.hip, spmv_mv_kernels.hip,
-// spmv_mvsym_kernels.hip).  Plain C++: no
+// spmv_mvr_kernels.hip, spmv_mvsym_kernels.hip).  Plain C++: no
 // HIP header, so that the host runtime (device_runtime.cpp) is compiled by the host compiler.
 #pragma once
 
@@ -136,6 +136,24 @@ enum class MvFamily {
 void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
                     const XcdSplit &xs);
 void spmv_mv_allow_lds(size_t bytes);
+
+// spmv_mvr_kernels.hip: the multi-vector product on ROW-MAJOR (interleaved) blocks, K = 1, 2, 4 or 8 vectors per
+// pass over the plain stream of a general tune: entry (i, j) of X at x[i * ldx + j], of Y at y[i * ldy + j]; x
+// and y point at the group's first vector.  The fields of MvArgs with that meaning of ldx and ldy (dvalues is
+// not read: symmetric streams are column-major business); `stage`: the x window of a row-block, xwin_len x K
+// doubles, is staged in LDS behind the K y tiles.
+struct MvrArgs : MvArgs {
+    uint32_t x16;              // 1: x and ldx * 8 are multiples of 16 -- the K doubles of a column load in pairs
+};
+void launch_spmv_mvr(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvrArgs &a,
+                     const XcdSplit &xs);
+void spmv_mvr_allow_lds(size_t bytes);
+// the steps around its row-block launches: y <- beta * y on the nvec vectors of the rows [lo, hi) (never the
+// padding behind them), and the sum of the carry slots (vector j's at carry + j * n_carry) of rows split over
+// several row-blocks
+void launch_scale_rm(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta);
+void launch_fixup_rm(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
+                     uint32_t n_carry, double *y, size_t ldy, double alpha, double beta);
 
 // spmv_mvsym_kernels.hip: the multi-vector product on symmetric streams with read-once passes
 // (SPX_PASS_SYMTILE, SPX_PASS_SYMSEG; spx.gpu.sym_matmat), atomic hand-over, over the plain pass table.

@@ -1,0 +1,223 @@
+// spmv_mvr_kernels.hip -- the multi-vector product Y <- alpha*A*X + beta*Y for gfx950 on ROW-MAJOR
+// (interleaved) blocks: entry (i, j) of X at x[i * ldx + j], of Y at y[i * ldy + j]; K vectors per pass over
+// the stream, K = 1, 2, 4 or 8 (one vector too: a remainder vector of such a block is still strided, which the
+// single-vector kernels cannot read).  The host side is device_spmm_rm (device_runtime.cpp).
+//
+// mv_body of spmv_mv_kernels.hip with the K-vector composition of spmv_mvr_device.hpp: the same row-blocks,
+// pass order and pairing, K-wide carry and LDS budget, over the PLAIN stream (passes, descs) of a general
+// tune.  What differs is where x and y lie: a lane loads the K contiguous doubles of each of its columns, the
+// staged x window is one copy of xwin_len consecutive rows of X, and the write-out walks the row-block's
+// n_rows x K entries of Y in memory order.
+//
+// The y tiles in LDS stay vector-major (vector j's rows at j * n_rows, the layout of mv_body) and are
+// transposed at the write-out: in a unit pass neighbouring lanes mostly own neighbouring rows, so the adds of
+// one vector (one ds_add_f64 per pass and vector) fall into consecutive banks, where tile[row * K + j] would
+// put the lanes 8 * K bytes apart (K = 8: every lane on one of four bank groups).  The adds run once per row
+// segment, the write-out once per row, so the conflicts are put where they are paid least often.  Only this
+// layout was built; the reasoning, not a measurement of both, decided (profiles/r15/MATMAT_RM.md).
+//
+// DET: as in spmv_mv_kernels.hip -- a copy of the K tiles per wavefront, summed in wavefront order: every
+// column is bit-identical to the single-vector product.
+#include "spmv_mvr_device.hpp"
+#include "spmv_launch.hpp"
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace spx {
+
+// One workgroup owns one row-block: LDS holds COPIES x K y tiles (copy c, vector j at (c * K + j) * n_rows),
+// then the x window (xwin_len x K doubles, row-major) where it is staged.
+template <int K, int WAVES, bool ACCUM, bool DET>
+__device__ __forceinline__ void mvr_body(const MvrArgs &a, const XcdSplit &xs, double *lds)
+{
+    constexpr int BLOCK_THREADS = 64 * WAVES;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t xcd = blockIdx.x & 7u;
+    const uint32_t rb_idx = xs.first[xcd] + (blockIdx.x >> 3);
+    if (rb_idx >= xs.first[xcd + 1u]) return;
+
+    const SpxPass *passes = a.passes + (size_t) rb_idx * a.pass_stride;
+    const SpxRowBlock rb = a.rbs[rb_idx];
+    SpxPass p0 = passes[wave];
+    SpxPass p1 = passes[wave + WAVES];                   // (the table is padded by one stride)
+    const int n_rows = rb.n_rows;
+    constexpr int COPIES = DET ? WAVES : 1;
+    const int tiles = K * n_rows;                        // doubles per copy
+    double *tile = lds + (DET ? wave * tiles : 0);
+    for (int i = threadIdx.x; i < COPIES * tiles; i += BLOCK_THREADS) lds[i] = 0.0;
+    double *win = lds + COPIES * tiles;
+    if (a.stage) {
+        // rows xwin_base .. xwin_base + xwin_len - 1 of X, K doubles of each: one run where ldx == K
+        const int xk = (int) rb.xwin_len * K;
+        const double *xw = a.x + (size_t) rb.xwin_base * a.ldx;
+        for (int e = threadIdx.x; e < xk; e += BLOCK_THREADS) win[e] = xw[(size_t) (e / K) * a.ldx + (e % K)];
+    }
+    __syncthreads();
+
+    // wave w takes passes w, w + WAVES, ..., two at a time when they have the same shape
+    const int n_pass = rb.n_pass;
+    for (int t = wave; t < n_pass; t += 2 * WAVES) {
+        const bool two = t + WAVES < n_pass;
+        if (two) {
+            if (same_shape(p0, p1)) {
+                run_pair<K>(a, rb, {p0, p1}, tile, win, lane);
+            } else {
+                run_pass<K>(a, rb, p0, tile, win, lane);
+                run_pass<K>(a, rb, p1, tile, win, lane);
+            }
+        } else {
+            run_pass<K>(a, rb, p0, tile, win, lane);
+        }
+        if (t + 2 * WAVES < n_pass) {
+            p0 = passes[t + 2 * WAVES];
+            p1 = passes[t + 3 * WAVES];
+        }
+    }
+    __syncthreads();
+    if (DET) {
+        // the wavefronts' copies, summed in wavefront order into the first one
+        for (int i = threadIdx.x; i < tiles; i += BLOCK_THREADS) {
+            double t = lds[i];
+#pragma unroll
+            for (int w = 1; w < COPIES; ++w) t += lds[w * tiles + i];
+            lds[i] = t;
+        }
+        __syncthreads();
+        tile = lds;
+    }
+
+    // ---- write the owned rows: entry e of the row-block's n_rows x K piece of Y, in memory order ----------
+    if (rb.flags & SPX_RB_SHARED) {
+        if (threadIdx.x < K) a.carry[(size_t) threadIdx.x * a.n_carry + rb.carry_slot] = tile[threadIdx.x * n_rows];
+    } else if (ACCUM) {
+        for (int e = threadIdx.x; e < tiles; e += BLOCK_THREADS) {
+            const int i = e / K, j = e % K;
+            atomicAdd(&a.y[((size_t) rb.row0 + i) * a.ldy + j], a.alpha * tile[j * n_rows + i]);
+        }
+    } else {
+        for (int e = threadIdx.x; e < tiles; e += BLOCK_THREADS) {
+            const int i = e / K, j = e % K;
+            double *yp = a.y + ((size_t) rb.row0 + i) * a.ldy + j;
+            double t = tile[j * n_rows + i];
+            t *= a.alpha;
+            if (a.beta != 0.0) t += a.beta * *yp;
+            *yp = t;
+        }
+    }
+}
+
+template <int K, int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_mvr_kernel(MvrArgs a, XcdSplit xs)
+{
+    extern __shared__ double lds_dyn[];      // K y tiles, then the x window
+    mvr_body<K, WAVES, false, false>(a, xs, lds_dyn);
+}
+
+template <int K, int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_mvr_accum_kernel(MvrArgs a, XcdSplit xs)
+{
+    extern __shared__ double lds_dyn[];
+    mvr_body<K, WAVES, true, false>(a, xs, lds_dyn);
+}
+
+template <int K, int WAVES>
+__global__ __launch_bounds__(64 * WAVES)
+void csx_spmv_mvr_det_kernel(MvrArgs a, XcdSplit xs)
+{
+    extern __shared__ double lds_dyn[];      // K y tiles per wavefront, then the x window
+    mvr_body<K, WAVES, false, true>(a, xs, lds_dyn);
+}
+
+// ---- the steps around the row-block launches, interleaved forms of csx_scale_kernel and csx_fixup_kernel ----
+
+// column slices in one launch, first step: y <- beta * y on the K vectors of the rows [lo, hi); one thread per
+// entry, never the padding behind a row's K
+__global__ void csx_scale_rm_kernel(double *y, size_t ldy, size_t lo, size_t n, uint32_t K, double beta)
+{
+    const size_t e = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * K) return;
+    double *yp = y + (lo + e / K) * ldy + e % K;
+    *yp = beta == 0.0 ? 0.0 : beta * *yp;
+}
+
+// rows split over several row-blocks: sum their partials (vector j's at carry + j * n_carry; blockIdx.y: j)
+__global__ void csx_fixup_rm_kernel(const SpxSharedRow *shared, uint32_t n_shared, const double *carry, uint32_t n_carry,
+                                    double *y, size_t ldy, double alpha, double beta)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_shared) return;
+    const size_t j = blockIdx.y;
+    const SpxSharedRow sr = shared[i];
+    const double *cj = carry + j * n_carry;
+    double *yp = y + (size_t) sr.row * ldy + j;
+    double s = 0.0;
+    for (uint32_t k = 0; k < sr.n_slots; ++k) s += cj[sr.first_slot + k];
+    *yp = (beta == 0.0) ? alpha * s : alpha * s + beta * *yp;
+}
+
+// ---- launchers ------------------------------------------------------------------------------
+
+typedef void (*MvrKernel)(MvrArgs, XcdSplit);
+
+template <int K, int WAVES>
+static MvrKernel mvr_kernel(MvFamily family)
+{
+    switch (family) {
+    case MvFamily::accum: return csx_spmv_mvr_accum_kernel<K, WAVES>;
+    case MvFamily::det: return csx_spmv_mvr_det_kernel<K, WAVES>;
+    case MvFamily::plain: break;
+    }
+    return csx_spmv_mvr_kernel<K, WAVES>;
+}
+
+template <int K>
+static MvrKernel mvr_kernel_w(MvFamily family, int waves)
+{
+    return waves == 2 ? mvr_kernel<K, 2>(family) : waves == 8 ? mvr_kernel<K, 8>(family) : mvr_kernel<K, 4>(family);
+}
+
+static MvrKernel mvr_kernel_kw(MvFamily family, int K, int waves)
+{
+    return K == 8 ? mvr_kernel_w<8>(family, waves) : K == 4 ? mvr_kernel_w<4>(family, waves)
+         : K == 2 ? mvr_kernel_w<2>(family, waves) : mvr_kernel_w<1>(family, waves);
+}
+
+void launch_spmv_mvr(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvrArgs &a,
+                     const XcdSplit &xs)
+{
+    const int w = (waves == 2 || waves == 8) ? waves : 4;
+    hipLaunchKernelGGL(mvr_kernel_kw(family, K, w), dim3(blocks), dim3(64 * w), lds_bytes, static_cast<hipStream_t>(stream),
+                       a, xs);
+}
+
+void spmv_mvr_allow_lds(size_t bytes)
+{
+    const int b = (int) bytes;
+    for (MvFamily f : {MvFamily::plain, MvFamily::accum, MvFamily::det})
+        for (int K : {1, 2, 4, 8})
+            for (int w : {2, 4, 8})
+                (void) hipFuncSetAttribute(reinterpret_cast<const void *>(mvr_kernel_kw(f, K, w)),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, b);
+}
+
+void launch_scale_rm(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta)
+{
+    const size_t t = 256, n = (hi - lo) * (size_t) nvec;
+    hipLaunchKernelGGL(csx_scale_rm_kernel, dim3((unsigned) ((n + t - 1) / t)), dim3((unsigned) t), 0,
+                       static_cast<hipStream_t>(stream), y, ldy, lo, hi - lo, (uint32_t) nvec, beta);
+}
+
+void launch_fixup_rm(void *stream, int nvec, const SpxSharedRow *shared, uint32_t n_shared, const double *carry,
+                     uint32_t n_carry, double *y, size_t ldy, double alpha, double beta)
+{
+    hipLaunchKernelGGL(csx_fixup_rm_kernel, dim3((n_shared + 63) / 64, (unsigned) nvec), dim3(64), 0,
+                       static_cast<hipStream_t>(stream), shared, n_shared, carry, n_carry, y, ldy, alpha, beta);
+}
+
+}  // namespace spx
