@@ -241,10 +241,13 @@ int spx_hip_matvec_trans_mode(const spx_matrix_t *A);
  * ranges, the wrong current device, a host-only matrix, (_vec) vectors whose sizes are not ncols / nrows, and a
  * matrix WITHOUT a float copy -- tuned or restored without the option, or tuned as a symmetric one without
  * spx.gpu.values_f32=all; the message says which.  There is no silent fp64 fallback.
- * Not provided: float forms of the multi-vector products (the one on read-once symmetric streams,
- * spx.gpu.sym_matmat, included), of the transposed, parts and dist products (spx_hip_matvec_trans_* on a symmetric
- * handle keeps running the fp64 forward product), host vectors, and a launch tune of their own for the float
- * kernels (they run with the wavefronts and the family measured for the fp64 product).
+ * The two multi-vector products have float forms as well: spx_hip_matmat_kernel_f32 and
+ * spx_hip_matmat_rm_kernel_f32, behind the fp64 multi-vector products below.
+ * Not provided: a float form of the multi-vector product on read-once symmetric streams (spx.gpu.sym_matmat: such a
+ * handle runs spx_hip_matmat_kernel_f32 column by column), of the transposed, parts and dist products
+ * (spx_hip_matvec_trans_* on a symmetric handle keeps running the fp64 forward product), host vectors, and a launch
+ * tune of their own for the float kernels (they run with the wavefronts and the family measured for the fp64
+ * product).
  */
 spx_error_t spx_hip_matvec_mult_f32(spx_value_t alpha, const spx_matrix_t *A, const spx_value_t *x_dev,
                                     spx_value_t *y_dev, void *stream);
@@ -315,6 +318,38 @@ spx_error_t spx_hip_matmat_rm_kernel(spx_value_t alpha, const spx_matrix_t *A, s
  * per wavefront) fit 80 KB of LDS -- the rule of spx_hip_matmat_group.  0: a symmetric handle, which the
  * product refuses; -1: a matrix without a device copy. */
 int spx_hip_matmat_rm_group(const spx_matrix_t *A);
+
+/* ---- multi-vector products with the float copy of the values ----------------------------
+ * Y <- alpha*fl32(A)*X + beta*Y for nvec vectors at once: spx_hip_matmat_kernel (column-major blocks) and
+ * spx_hip_matmat_rm_kernel (row-major blocks) through kernels that read the float copy of the values
+ * (spx.gpu.values_f32, see "product with a float copy of the values" above).  For a block solver with an inner
+ * mixed-precision solve: one pass over the stream serves a group of vectors AND reads half the value bytes.
+ * Column j of Y is what spx_hip_matvec_kernel_f32 writes for column j of X; everything else is the fp64 call's of
+ * the same layout: the rows written on a row slice or (column-major) an attached matrix, beta == 0 never reads Y,
+ * the padding is never read or written, nvec == 0 does nothing, X and Y must not overlap, the call only enqueues
+ * and allocates nothing (hipGraph-capturable), the handle's single-stream rule (the carry scratch is shared with
+ * the other products), it counts as a product for spx_mat_set_entry's wait, and with
+ * spx.gpu.deterministic=true every column is bit-identical to spx_hip_matvec_kernel_f32's.  Vectors, the x
+ * windows and y tiles in LDS, products and sums are fp64; the kernel family, wavefronts, LDS and staging are
+ * those of the handle's fp64 multi-vector product.
+ * Column-major groups: spx_hip_matmat_group_f32(A) vectors per pass -- spx_hip_matmat_group(A) on general tunes
+ * and on symmetric ones without tiles or read-once segments (spx.gpu.sym_once=false: the diagonal is rounded in
+ * registers); 1 on symmetric tunes with tiles or read-once segments, spx.gpu.sym_matmat=true included: one
+ * spx_hip_matvec_kernel_f32 per column -- still fl32(A), exact, no faster.  The fp64 group kernel never runs.
+ * Row-major groups: spx_hip_matmat_rm_group(A).
+ * SPX_FAILURE (through the error handler, nothing enqueued, Y untouched): every refusal of the fp64 call of the
+ * same layout (row-major: a symmetric handle and an attached matrix among them), and a handle WITHOUT a float copy;
+ * the message says which option was missing.  There is no fp64 fallback.
+ */
+spx_error_t spx_hip_matmat_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                      const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                      spx_value_t *Y_dev, size_t ldy, void *stream);
+spx_error_t spx_hip_matmat_rm_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                         const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                         spx_value_t *Y_dev, size_t ldy, void *stream);
+/* Diagnostic: vectors per pass of spx_hip_matmat_kernel_f32 (see above); 0: no float copy; -1: a NULL handle or
+ * a matrix without a device copy. */
+int spx_hip_matmat_group_f32(const spx_matrix_t *A);
 
 /* ---- device-resident vectors ---------------------------------------------------
  * HBM counterparts of the reference's host vector helpers (spx_vec_init,

@@ -408,6 +408,9 @@ class Matrix:
         """Y <- alpha*A*X + beta*Y for torch float64 tensors on the matrix' device: X of shape (nvec, ncols),
         Y of shape (nvec, nrows), each row one vector, stride(1) == 1 and stride(0) the leading dimension.
         `stream`: a torch stream (default: the current one of Y's device).  Returns Y."""
+        return self._matmat(self.hip_matmat_kernel, alpha, X, beta, Y, stream)
+
+    def _matmat(self, kernel, alpha, X, beta, Y, stream):
         import torch
         pairs = (("X", X, self.ncols), ("Y", Y, self.nrows))
         for name, t, n in pairs:
@@ -435,8 +438,32 @@ class Matrix:
         ldx = max(int(X.stride(0)), self.ncols) if nvec > 1 else max(self.ncols, 1)
         ldy = max(int(Y.stride(0)), self.nrows) if nvec > 1 else max(self.nrows, 1)
         st = stream if stream is not None else torch.cuda.current_stream(Y.device)
-        self.hip_matmat_kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
+        kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
         return Y
+
+    def hip_matmat_kernel_f32(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
+        """``spx_hip_matmat_kernel_f32``: Y <- alpha*fl32(A)*X + beta*Y for nvec column-major vectors in HBM, with
+        the float copy of the values (``spx.gpu.values_f32``); the arguments of ``hip_matmat_kernel``."""
+        L = lib()
+        L.spx_hip_matmat_kernel_f32.restype = C.c_int
+        L.spx_hip_matmat_kernel_f32.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+        rc = L.spx_hip_matmat_kernel_f32(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
+        if rc != SPX_SUCCESS:
+            raise SpxError("spx_hip_matmat_kernel_f32 failed (see stderr)")
+
+    def matmat_group_f32(self):
+        """``spx_hip_matmat_group_f32``: vectors one pass of ``matmat_f32`` over the stream serves (1: one float
+        product per vector; 0: no float copy; -1: no device copy)."""
+        L = lib()
+        L.spx_hip_matmat_group_f32.restype = C.c_int
+        L.spx_hip_matmat_group_f32.argtypes = [C.c_void_p]
+        return int(L.spx_hip_matmat_group_f32(C.c_void_p(self.handle)))
+
+    def matmat_f32(self, alpha, X, beta, Y, stream=None):
+        """Y <- alpha*fl32(A)*X + beta*Y: ``matmat`` (its tensors, checks and return value) with the float copy
+        of the values.  SpxError on a matrix without one."""
+        return self._matmat(self.hip_matmat_kernel_f32, alpha, X, beta, Y, stream)
 
     def hip_matmat_rm_kernel(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
         """``spx_hip_matmat_rm_kernel``: Y <- alpha*A*X + beta*Y for nvec vectors of row-major (interleaved)
@@ -463,6 +490,9 @@ class Matrix:
         X of shape (ncols, nvec), Y of shape (nrows, nvec), each column one vector, stride(1) == 1 and
         stride(0) >= nvec the leading dimension.  General tunes only.  `stream`: a torch stream (default: the
         current one of Y's device).  Returns Y."""
+        return self._matmat_rm(self.hip_matmat_rm_kernel, alpha, X, beta, Y, stream)
+
+    def _matmat_rm(self, kernel, alpha, X, beta, Y, stream):
         import torch
         pairs = (("X", X, self.ncols), ("Y", Y, self.nrows))
         for name, t, n in pairs:
@@ -491,8 +521,26 @@ class Matrix:
         ldx = max(int(X.stride(0)), nvec) if self.ncols > 1 else max(nvec, 1)
         ldy = max(int(Y.stride(0)), nvec) if self.nrows > 1 else max(nvec, 1)
         st = stream if stream is not None else torch.cuda.current_stream(Y.device)
-        self.hip_matmat_rm_kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
+        kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
         return Y
+
+    def hip_matmat_rm_kernel_f32(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
+        """``spx_hip_matmat_rm_kernel_f32``: Y <- alpha*fl32(A)*X + beta*Y for nvec vectors of row-major
+        (interleaved) blocks in HBM, with the float copy of the values (``spx.gpu.values_f32``); the arguments of
+        ``hip_matmat_rm_kernel``.  General tunes only."""
+        L = lib()
+        L.spx_hip_matmat_rm_kernel_f32.restype = C.c_int
+        L.spx_hip_matmat_rm_kernel_f32.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+        rc = L.spx_hip_matmat_rm_kernel_f32(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
+        if rc != SPX_SUCCESS:
+            raise SpxError("spx_hip_matmat_rm_kernel_f32 failed (see stderr)")
+
+    def matmat_rm_f32(self, alpha, X, beta, Y, stream=None):
+        """Y <- alpha*fl32(A)*X + beta*Y: ``matmat_rm`` (its tensors, checks and return value) with the float
+        copy of the values.  General tunes only; SpxError on a matrix without a float copy.  The group is
+        ``matmat_rm_group()``."""
+        return self._matmat_rm(self.hip_matmat_rm_kernel_f32, alpha, X, beta, Y, stream)
 
     def info(self):
         inf = HipInfo()

@@ -2369,10 +2369,12 @@ try {
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
-spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+// spx_hip_matmat_kernel, and with `f32` spx_hip_matmat_kernel_f32: one set of checks, then the product that
+// reads the doubles or the one that reads the float copy (refused where there is none: no fp64 fallback)
+static spx_error_t matmat_checked(bool f32, spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                   const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                   spx_value_t *Y_dev, size_t ldy, void *stream)
-try {
+{
     if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
     if (!A->dev) {
         SETERROR_1(SPX_ERR_TUNED_MAT,
@@ -2400,12 +2402,26 @@ try {
         return SPX_FAILURE;
     }
     try {
-        device_spmm(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
+        (f32 ? device_spmm_f32 : device_spmm)(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
     } catch (const FatalError &e) {
         SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
         return SPX_FAILURE;
     }
     return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                  const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                  spx_value_t *Y_dev, size_t ldy, void *stream)
+try {
+    return matmat_checked(false, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_matmat_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                      const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                      spx_value_t *Y_dev, size_t ldy, void *stream)
+try {
+    return matmat_checked(true, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
 int spx_hip_matmat_group(const spx_matrix_t *A)
@@ -2413,10 +2429,16 @@ try {
     return A && A->dev ? device_mv_group(A->dev) : -1;
 } SPX_C_BOUNDARY(return -1;)
 
-spx_error_t spx_hip_matmat_rm_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+int spx_hip_matmat_group_f32(const spx_matrix_t *A)
+try {
+    return A && A->dev ? device_mv_group_f32(A->dev) : -1;
+} SPX_C_BOUNDARY(return -1;)
+
+// spx_hip_matmat_rm_kernel, and with `f32` spx_hip_matmat_rm_kernel_f32
+static spx_error_t matmat_rm_checked(bool f32, spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                      const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                      spx_value_t *Y_dev, size_t ldy, void *stream)
-try {
+{
     if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
     if (!A->dev) {
         SETERROR_1(SPX_ERR_TUNED_MAT,
@@ -2455,12 +2477,26 @@ try {
         return SPX_FAILURE;
     }
     try {
-        device_spmm_rm(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
+        (f32 ? device_spmm_rm_f32 : device_spmm_rm)(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
     } catch (const FatalError &e) {
         SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
         return SPX_FAILURE;
     }
     return SPX_SUCCESS;
+}
+
+spx_error_t spx_hip_matmat_rm_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                     const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                     spx_value_t *Y_dev, size_t ldy, void *stream)
+try {
+    return matmat_rm_checked(false, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_matmat_rm_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+                                         const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
+                                         spx_value_t *Y_dev, size_t ldy, void *stream)
+try {
+    return matmat_rm_checked(true, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
 int spx_hip_matmat_rm_group(const spx_matrix_t *A)

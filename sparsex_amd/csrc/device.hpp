@@ -69,6 +69,18 @@ void device_spmm_rm(DeviceMatrix *m, double alpha, const double *d_X, size_t ldx
                     double *d_Y, size_t ldy, void *stream);
 // vectors per pass of that product: 8, 4, 2 or 1; 0: a stream it does not serve (symmetric)
 int device_mv_group_rm(const DeviceMatrix *m);
+// The two multi-vector products with fl32(A), through the kernels that read the float twin of the values
+// (spmv_mv_f32_kernels.hip, spmv_mvr_f32_kernels.hip): column j is what device_spmv_f32 writes for column j of X.
+// The groups, families, wavefronts, LDS and staging of device_spmm / device_spmm_rm; FatalError where there is no
+// twin (and every FatalError of the fp64 product of the same layout).  device_mv_group_f32: device_mv_group where
+// the plain K-vector kernels run; 1 on streams with symmetric tiles or read-once segments, spx.gpu.sym_matmat or
+// not (one device_spmv_f32 per column: never the fp64 group kernel); 0 without a twin.  The row-major group is
+// device_mv_group_rm.
+void device_spmm_f32(DeviceMatrix *m, double alpha, const double *d_X, size_t ldx, size_t nvec, double beta,
+                     double *d_Y, size_t ldy, void *stream);
+int device_mv_group_f32(const DeviceMatrix *m);
+void device_spmm_rm_f32(DeviceMatrix *m, double alpha, const double *d_X, size_t ldx, size_t nvec, double beta,
+                        double *d_Y, size_t ldy, void *stream);
 
 // The product in K launches over consecutive parts of the row-blocks (equal work each), so that
 // the exchange of a row-partitioned matrix can start on the rows of part k while part k + 1 is

@@ -704,7 +704,11 @@ void device_build_values_f32(DeviceMatrix *m)
         throw;
     }
     // (the float kernels are allowed the dynamic LDS of their fp64 families where those are: spmv_allow_lds,
-    // spmv_xw_allow_lds)
+    // spmv_xw_allow_lds; the float instances of the K-vector kernels here, where the stream runs them)
+    if (!m->has_tiles && m->carry_mv) {
+        spmv_mv_f32_allow_lds(160u * 1024u);
+        if (!m->symmetric) spmv_mvr_f32_allow_lds(160u * 1024u);
+    }
 }
 
 int64_t device_values_f32_bytes(const DeviceMatrix *m)
@@ -735,12 +739,18 @@ double device_time_narrow_values(DeviceMatrix *m)
     return 1e-3 * ms;
 }
 
-// y <- alpha*fl32(A)*x + beta*y: device_spmv through the kernels that read the float twin
-void device_spmv_f32(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_)
+// the float copy a float product needs, or the message saying which option was missing
+static void need_values_f32(const DeviceMatrix *m)
 {
     if (!m->values_f32)
         throw FatalError(m->symmetric ? "no float copy of the values: this matrix was tuned as a symmetric one, and tuned or restored without spx.gpu.values_f32=all"
                                       : "no float copy of the values: the matrix was tuned or restored without spx.gpu.values_f32=true (or all)");
+}
+
+// y <- alpha*fl32(A)*x + beta*y: device_spmv through the kernels that read the float twin
+void device_spmv_f32(DeviceMatrix *m, double alpha, const double *d_x, double beta, double *d_y, void *stream_)
+{
+    need_values_f32(m);
     device_product(m, 1, alpha, d_x, 0, beta, d_y, 0, stream_, nullptr, true);
 }
 
@@ -913,12 +923,17 @@ static uint32_t mv_n_carry(const DeviceMatrix *m) { return m->n_carry ? m->n_car
 
 // launch_rowblocks for K >= 2 vectors: the plain stream through the kernels of spmv_mv_kernels.hip; `rm`: for K >= 1
 // vectors of row-major blocks (general streams only: device_spmm_rm) through those of spmv_mvr_kernels.hip
+// (`f32`, streams with a float twin: the same family, wavefronts, LDS and staging, the kernel that reads the twin --
+// spmv_mv_f32_kernels.hip, spmv_mvr_f32_kernels.hip; csx_spmv_mvsym_kernel has no float form)
 static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &a, size_t ldx, size_t ldy,
-                                const XcdSplit &xcd_now, uint32_t blocks, void *stream, bool rm)
+                                const XcdSplit &xcd_now, uint32_t blocks, void *stream, bool rm, bool f32 = false)
 {
     if (!blocks) return;
+    if (f32 && !m->values_f32) throw FatalError("no float copy of the values");
+    if (f32 && m->has_tiles) throw FatalError("the float multi-vector product has no kernel for read-once passes");
     MvArgs mv{};
     static_cast<StreamArgs &>(mv) = a;
+    if (f32) mv.values = reinterpret_cast<const double *>(m->values_f32);     // (StreamArgs::values of a float launch)
     mv.x = a.x; mv.y = a.y; mv.ldx = ldx; mv.ldy = ldy;
     mv.carry = m->carry_mv; mv.n_carry = mv_n_carry(m);
     mv.dvalues = a.dvalues; mv.alpha = a.alpha; mv.beta = a.beta; mv.pass_stride = a.pass_stride;
@@ -930,7 +945,8 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
         mr.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
         mr.x16 = ((uintptr_t) a.x % 16u == 0 && (ldx * sizeof(double)) % 16u == 0) ? 1u : 0u;
         const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
-        launch_spmv_mvr(family, K, m->waves, blocks, mv_lds_bytes(m, K, mr.stage != 0), stream, mr, xcd_now);
+        (f32 ? launch_spmv_mvr_f32 : launch_spmv_mvr)(family, K, m->waves, blocks, mv_lds_bytes(m, K, mr.stage != 0), stream,
+                                                      mr, xcd_now);
         return;
     }
     if (m->has_tiles) {
@@ -946,7 +962,8 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
     // the K x windows in LDS where they fit next to the tiles; else SPX_PASS_GATHER_LDS gathers through L2
     mv.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
     const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
-    launch_spmv_mv(family, K, m->waves, blocks, mv_lds_bytes(m, K, mv.stage != 0), stream, mv, xcd_now);
+    (f32 ? launch_spmv_mv_f32 : launch_spmv_mv)(family, K, m->waves, blocks, mv_lds_bytes(m, K, mv.stage != 0), stream, mv,
+                                                xcd_now);
 }
 
 // Y <- alpha*A*X + beta*Y for K vectors (column-major: vector j of X at X + j * ldx, of Y at Y + j * ldy) in one
@@ -1013,7 +1030,7 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
         const XcdSplit &split = part ? part->split : m->xcd_split[ph];
         const uint32_t blocks = 8u * (part ? part->longest : m->xcd_longest[ph]);
         if (K == 1 && !rm) need_symfix |= launch_rowblocks(m, a, split, blocks, stream_, f32);
-        else launch_rowblocks_mv(m, K, a, ldx, ldy, split, blocks, stream_, rm);
+        else launch_rowblocks_mv(m, K, a, ldx, ldy, split, blocks, stream_, rm, f32);
     }
     if (part && !part->last) {
         HIP_CHECK(hipGetLastError());
@@ -1045,6 +1062,31 @@ void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, siz
     }
 }
 
+// the group of device_spmm_f32: device_mv_group's where the plain K-vector kernels run (general streams, symmetric
+// ones without tiles or read-once segments); 1 where the stream has tiles or read-once segments, spx.gpu.sym_matmat
+// or not (csx_spmv_mvsym_kernel has no float form: one single float product per column); 0 without a float copy
+int device_mv_group_f32(const DeviceMatrix *m)
+{
+    if (!m->values_f32) return 0;
+    if (m->has_tiles) return 1;
+    return device_mv_group(m);
+}
+
+// Y <- alpha*fl32(A)*X + beta*Y for nvec column-major vectors: the groups of device_spmm through the kernels that
+// read the float twin; column by column through device_spmv_f32's kernels where device_mv_group_f32 is 1
+void device_spmm_f32(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
+                     size_t ldy, void *stream_)
+{
+    need_values_f32(m);
+    const int G = device_mv_group_f32(m);
+    for (size_t j = 0; j < nvec;) {
+        int K = G;
+        while (K > 1 && (size_t) K > nvec - j) K /= 2;
+        device_product(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_, nullptr, true);
+        j += (size_t) K;
+    }
+}
+
 // the widest group of the row-major product: the budget and the formula of device_mv_group for general streams
 // (mv_lds_bytes: K y tiles per copy), 1 where only the one-vector instance fits; 0: a stream this product does not
 // serve (symmetric, or without the K-wide carry)
@@ -1068,6 +1110,21 @@ void device_spmm_rm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, 
         int K = G;
         while (K > 1 && (size_t) K > nvec - j) K /= 2;
         device_product(m, K, alpha, X + j, ldx, beta, Y + j, ldy, stream_, nullptr, false, true);
+        j += (size_t) K;
+    }
+}
+
+// ... through the kernels that read the float twin: Y <- alpha*fl32(A)*X + beta*Y, the same groups
+void device_spmm_rm_f32(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
+                        size_t ldy, void *stream_)
+{
+    const int G = device_mv_group_rm(m);
+    if (G < 1) throw FatalError("the row-major multi-vector product serves general (non-symmetric) tunes only");
+    need_values_f32(m);
+    for (size_t j = 0; j < nvec;) {
+        int K = G;
+        while (K > 1 && (size_t) K > nvec - j) K /= 2;
+        device_product(m, K, alpha, X + j, ldx, beta, Y + j, ldy, stream_, nullptr, true, true);
         j += (size_t) K;
     }
 }

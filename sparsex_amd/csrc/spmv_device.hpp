@@ -123,6 +123,21 @@ __device__ __forceinline__ PassValues<W, V> load_values(const StreamArgs &a, con
     return v;
 }
 
+// the values of a pass as doubles (V = double: as they are): the members load_values wrote, W / 2 pairs and the
+// odd last one
+template <int W, class V>
+__device__ __forceinline__ PassValues<W> widened(const PassValues<W, V> &v)
+{
+    PassValues<W> d;
+#pragma unroll
+    for (int p = 0; p < W / 2; ++p) {
+        d.v2[p].x = (double) v.v2[p].x;
+        d.v2[p].y = (double) v.v2[p].y;
+    }
+    if (W & 1) d.v1 = (double) v.v1;
+    return d;
+}
+
 // descriptor bits -> where segment `seg` of the row-block (only its low 16 bits count) lies: its row in the
 // row-block (`row0`: the first row of the pass' part of it, SpxPass::elem0) and its first column, as an
 // offset from the unit's first column
@@ -259,7 +274,7 @@ __device__ __forceinline__ void unit_passes(const KernelArgs &a, const SpxRowBlo
 // K vectors (column-major: vector j of x at a.x + j * a.ldx): index and values once, then for every vector
 // its x, the dot products and the adds to ITS y tile (vector j at tile + j * n_rows).  `win`: the K staged x
 // windows (vector j at win + j * xwin_len) where MvArgs::stage says so, else the SPX_PASS_GATHER_LDS offsets
-// gather through L2 relative to xwin_base.  (V: so that run_units names both compositions alike; doubles only)
+// gather through L2 relative to xwin_base.  V: the type of the values, as in the single-vector composition.
 template <int W, int B, int G, int K, class V = double>
 __device__ __forceinline__ void unit_passes(const MvArgs &a, const SpxRowBlock &rb, const SpxPass (&ps)[B],
                                             double *tile, const double *win, int lane)
@@ -274,9 +289,10 @@ __device__ __forceinline__ void unit_passes(const MvArgs &a, const SpxRowBlock &
         l[b] = active[b] ? (uint32_t) lane : 0u;         // idle lanes shadow lane 0
         SPX_LOAD_INDEX(W, G, a, rb, ps[b], active[b], l[b], lane, q[b], goff[b]);
     }
+    // (widened once, in front of the K vectors: every vector multiplies with the same doubles)
     PassValues<W> v[B];
 #pragma unroll
-    for (int b = 0; b < B; ++b) v[b] = load_values<W>(a, rb, ps[b], l[b]);
+    for (int b = 0; b < B; ++b) v[b] = widened<W, V>(load_values<W, V>(a, rb, ps[b], l[b]));
     // the lane's row and where its x lies: the same for every vector of the group
     int row[B], len[B];
     uint32_t col[B];

@@ -1,7 +1,7 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the seven interpreter translation
+// XCD-aware row-block order, the kernel families and the launchers of the nine interpreter translation
 // units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_t_kernels.hip, spmv_mv_kernels.hip,
-// spmv_mvr_kernels.hip, spmv_mvsym_kernels.hip).  Plain C++: no
+// spmv_mv_f32_kernels.hip, spmv_mvr_kernels.hip, spmv_mvr_f32_kernels.hip, spmv_mvsym_kernels.hip).  Plain C++: no
 // HIP header, so that the host runtime (device_runtime.cpp) is compiled by the host compiler.
 #pragma once
 
@@ -136,6 +136,11 @@ enum class MvFamily {
 void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
                     const XcdSplit &xs);
 void spmv_mv_allow_lds(size_t bytes);
+// spmv_mv_f32_kernels.hip: the same kernels reading the float twin of the values (spx.gpu.values_f32) -- a.values
+// then points at that array of floats; everything else, a.dvalues included, as above
+void launch_spmv_mv_f32(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
+                        const XcdSplit &xs);
+void spmv_mv_f32_allow_lds(size_t bytes);
 
 // spmv_mvr_kernels.hip: the multi-vector product on ROW-MAJOR (interleaved) blocks, K = 1, 2, 4 or 8 vectors per
 // pass over the plain stream of a general tune: entry (i, j) of X at x[i * ldx + j], of Y at y[i * ldy + j]; x
@@ -148,6 +153,10 @@ struct MvrArgs : MvArgs {
 void launch_spmv_mvr(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvrArgs &a,
                      const XcdSplit &xs);
 void spmv_mvr_allow_lds(size_t bytes);
+// spmv_mvr_f32_kernels.hip: the same kernels reading the float twin of the values (a.values points at the floats)
+void launch_spmv_mvr_f32(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream,
+                         const MvrArgs &a, const XcdSplit &xs);
+void spmv_mvr_f32_allow_lds(size_t bytes);
 // the steps around its row-block launches: y <- beta * y on the nvec vectors of the rows [lo, hi) (never the
 // padding behind them), and the sum of the carry slots (vector j's at carry + j * n_carry) of rows split over
 // several row-blocks

@@ -28,87 +28,7 @@
 
 namespace spx {
 
-// One workgroup owns one row-block: LDS holds COPIES x K y tiles (copy c, vector j at (c * K + j) * n_rows),
-// then the x window (xwin_len x K doubles, row-major) where it is staged.
-template <int K, int WAVES, bool ACCUM, bool DET>
-__device__ __forceinline__ void mvr_body(const MvrArgs &a, const XcdSplit &xs, double *lds)
-{
-    constexpr int BLOCK_THREADS = 64 * WAVES;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t xcd = blockIdx.x & 7u;
-    const uint32_t rb_idx = xs.first[xcd] + (blockIdx.x >> 3);
-    if (rb_idx >= xs.first[xcd + 1u]) return;
-
-    const SpxPass *passes = a.passes + (size_t) rb_idx * a.pass_stride;
-    const SpxRowBlock rb = a.rbs[rb_idx];
-    SpxPass p0 = passes[wave];
-    SpxPass p1 = passes[wave + WAVES];                   // (the table is padded by one stride)
-    const int n_rows = rb.n_rows;
-    constexpr int COPIES = DET ? WAVES : 1;
-    const int tiles = K * n_rows;                        // doubles per copy
-    double *tile = lds + (DET ? wave * tiles : 0);
-    for (int i = threadIdx.x; i < COPIES * tiles; i += BLOCK_THREADS) lds[i] = 0.0;
-    double *win = lds + COPIES * tiles;
-    if (a.stage) {
-        // rows xwin_base .. xwin_base + xwin_len - 1 of X, K doubles of each: one run where ldx == K
-        const int xk = (int) rb.xwin_len * K;
-        const double *xw = a.x + (size_t) rb.xwin_base * a.ldx;
-        for (int e = threadIdx.x; e < xk; e += BLOCK_THREADS) win[e] = xw[(size_t) (e / K) * a.ldx + (e % K)];
-    }
-    __syncthreads();
-
-    // wave w takes passes w, w + WAVES, ..., two at a time when they have the same shape
-    const int n_pass = rb.n_pass;
-    for (int t = wave; t < n_pass; t += 2 * WAVES) {
-        const bool two = t + WAVES < n_pass;
-        if (two) {
-            if (same_shape(p0, p1)) {
-                run_pair<K>(a, rb, {p0, p1}, tile, win, lane);
-            } else {
-                run_pass<K>(a, rb, p0, tile, win, lane);
-                run_pass<K>(a, rb, p1, tile, win, lane);
-            }
-        } else {
-            run_pass<K>(a, rb, p0, tile, win, lane);
-        }
-        if (t + 2 * WAVES < n_pass) {
-            p0 = passes[t + 2 * WAVES];
-            p1 = passes[t + 3 * WAVES];
-        }
-    }
-    __syncthreads();
-    if (DET) {
-        // the wavefronts' copies, summed in wavefront order into the first one
-        for (int i = threadIdx.x; i < tiles; i += BLOCK_THREADS) {
-            double t = lds[i];
-#pragma unroll
-            for (int w = 1; w < COPIES; ++w) t += lds[w * tiles + i];
-            lds[i] = t;
-        }
-        __syncthreads();
-        tile = lds;
-    }
-
-    // ---- write the owned rows: entry e of the row-block's n_rows x K piece of Y, in memory order ----------
-    if (rb.flags & SPX_RB_SHARED) {
-        if (threadIdx.x < K) a.carry[(size_t) threadIdx.x * a.n_carry + rb.carry_slot] = tile[threadIdx.x * n_rows];
-    } else if (ACCUM) {
-        for (int e = threadIdx.x; e < tiles; e += BLOCK_THREADS) {
-            const int i = e / K, j = e % K;
-            atomicAdd(&a.y[((size_t) rb.row0 + i) * a.ldy + j], a.alpha * tile[j * n_rows + i]);
-        }
-    } else {
-        for (int e = threadIdx.x; e < tiles; e += BLOCK_THREADS) {
-            const int i = e / K, j = e % K;
-            double *yp = a.y + ((size_t) rb.row0 + i) * a.ldy + j;
-            double t = tile[j * n_rows + i];
-            t *= a.alpha;
-            if (a.beta != 0.0) t += a.beta * *yp;
-            *yp = t;
-        }
-    }
-}
+// (mvr_body, the body of the kernels below and of their float forms in spmv_mvr_f32_kernels.hip: spmv_mvr_device.hpp)
 
 template <int K, int WAVES>
 __global__ __launch_bounds__(64 * WAVES)

@@ -12,6 +12,10 @@ their spread ((max - min) / median) are reported.  Every column of (a) and of (b
 is timed (relative 1e-6, the reference's criterion).  One JSON line per config:
 
     python3 tools/matmat_rm_bench.py [--configs cant,nd24k,webbase,e240] [--edge 240]
+
+--f32: spx_hip_matmat_rm_kernel_f32 (the float copy of the values, spx.gpu.values_f32=true) against
+spx_hip_matmat_rm_kernel on one handle, at the handle's group (or --k), with the variants, gates and protocol of
+tools/matmat_bench.py --f32 (whose code runs), itself that of tools/f32_bench.py.
 """
 import argparse
 import json
@@ -25,6 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import bench  # noqa: E402  (make_workload, tune, ALPHA, BATCHES: the bench protocol)
+import matmat_bench  # noqa: E402  (run_f32: the --f32 variant of both tools)
 
 KS = (1, 2, 4, 8)
 
@@ -146,12 +151,23 @@ def main():
     ap.add_argument("--edge", type=int, default=bench.DEFAULT_EDGE)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--f32", action="store_true",
+                    help="the float row-major block product against the fp64 one on one handle (see above)")
+    ap.add_argument("--no-plain", action="store_true", help="--f32: no second handle tuned without the copy")
+    ap.add_argument("--first", choices=["without", "with"], default="without",
+                    help="--f32: which handle is tuned first and whose fp64 block is timed first in every round")
+    ap.add_argument("--k", default=None, help="--f32: comma-separated block widths instead of the handle's group")
     args = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
     ok = True
     for cfg in args.configs.split(","):
-        line = json.dumps(run(torch, cfg, args.edge, args.threads))
+        if args.f32:
+            ks = tuple(int(k) for k in args.k.split(",")) if args.k else None
+            line = json.dumps(matmat_bench.run_f32(torch, cfg, CONFIGS[cfg], False, {}, args.edge, args.threads, "rm", ks,
+                                                   not args.no_plain, args.first))
+        else:
+            line = json.dumps(run(torch, cfg, args.edge, args.threads))
         print(line, flush=True)
         ok &= json.loads(line)["parity"]
         if args.out:
