@@ -385,16 +385,19 @@ class Matrix:
         self.hip_matvec_kernel_f32(alpha, x.data_ptr(), beta, y.data_ptr(), st.cuda_stream)
         return y
 
+    def _hip_matmat(self, name, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream):
+        """One of the four ``spx_hip_matmat*_kernel*`` entries, which take the same arguments."""
+        f = getattr(lib(), name)
+        f.restype = C.c_int
+        f.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                      C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
+        if f(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream) != SPX_SUCCESS:
+            raise SpxError("%s failed (see stderr)" % name)
+
     def hip_matmat_kernel(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
         """``spx_hip_matmat_kernel``: Y <- alpha*A*X + beta*Y for nvec column-major vectors in HBM
         (vector j of X at x_ptr + 8*j*ldx, of Y at y_ptr + 8*j*ldy)."""
-        L = lib()
-        L.spx_hip_matmat_kernel.restype = C.c_int
-        L.spx_hip_matmat_kernel.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
-        rc = L.spx_hip_matmat_kernel(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
-        if rc != SPX_SUCCESS:
-            raise SpxError("spx_hip_matmat_kernel failed (see stderr)")
+        self._hip_matmat("spx_hip_matmat_kernel", alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream)
 
     def matmat_group(self):
         """``spx_hip_matmat_group``: vectors one pass over the stream serves (1: one product per vector;
@@ -410,22 +413,35 @@ class Matrix:
         `stream`: a torch stream (default: the current one of Y's device).  Returns Y."""
         return self._matmat(self.hip_matmat_kernel, alpha, X, beta, Y, stream)
 
-    def _matmat(self, kernel, alpha, X, beta, Y, stream):
+    def _matmat(self, kernel, alpha, X, beta, Y, stream, rm=False):
+        """The tensor checks and the call of ``matmat`` and its kin; `rm`: the tensors of ``matmat_rm``, whose
+        axis 1 counts the vectors where the column-major ones' axis 0 does."""
         import torch
+        vec, along = (1, 0) if rm else (0, 1)
         pairs = (("X", X, self.ncols), ("Y", Y, self.nrows))
+
+        def check_strides(name, t):
+            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+                raise ValueError("%s needs stride(1) == 1, not %d" % (name, t.stride(1)))
+            if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+                raise ValueError("%s: stride(0) %d is below the %s %d"
+                                 % (name, t.stride(0), "number of vectors" if rm else "vector length", t.shape[1]))
+
         for name, t, n in pairs:
             if not isinstance(t, torch.Tensor):
                 raise ValueError("%s must be a torch tensor" % name)
             if t.dtype != torch.float64:
                 raise ValueError("%s must be float64, not %s" % (name, t.dtype))
-            if t.dim() != 2 or t.shape[1] != n:
-                raise ValueError("%s must have the shape (nvec, %d), not %s" % (name, n, tuple(t.shape)))
-            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
-                raise ValueError("%s needs stride(1) == 1, not %d" % (name, t.stride(1)))
-            if t.shape[0] > 1 and t.stride(0) < n:
-                raise ValueError("%s: stride(0) %d is below the vector length %d" % (name, t.stride(0), n))
-        if X.shape[0] != Y.shape[0]:
-            raise ValueError("X holds %d vectors, Y %d" % (X.shape[0], Y.shape[0]))
+            if t.dim() != 2 or t.shape[along] != n:
+                raise ValueError("%s must have the shape %s, not %s"
+                                 % (name, "(%d, nvec)" % n if rm else "(nvec, %d)" % n, tuple(t.shape)))
+            if not rm:
+                check_strides(name, t)
+        if X.shape[vec] != Y.shape[vec]:
+            raise ValueError("X holds %d vectors, Y %d" % (X.shape[vec], Y.shape[vec]))
+        if rm:
+            for name, t, n in pairs:
+                check_strides(name, t)
         for name, t, n in pairs:
             if t.device.type != "cuda":
                 raise ValueError("%s must live on the matrix' HIP device, not on %s" % (name, t.device))
@@ -434,23 +450,16 @@ class Matrix:
         inf = self.info()
         if inf.on_device and X.device.index != inf.device:
             raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, X.device))
-        nvec = int(X.shape[0])
-        ldx = max(int(X.stride(0)), self.ncols) if nvec > 1 else max(self.ncols, 1)
-        ldy = max(int(Y.stride(0)), self.nrows) if nvec > 1 else max(self.nrows, 1)
+        # the leading dimension: stride(0), which a tensor of one row (or of rows of one entry) may report as anything
+        ldx, ldy = (max(int(t.stride(0)), t.shape[1]) if t.shape[0] > 1 else max(t.shape[1], 1) for t in (X, Y))
         st = stream if stream is not None else torch.cuda.current_stream(Y.device)
-        kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
+        kernel(alpha, X.data_ptr(), ldx, int(X.shape[vec]), beta, Y.data_ptr(), ldy, st.cuda_stream)
         return Y
 
     def hip_matmat_kernel_f32(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
         """``spx_hip_matmat_kernel_f32``: Y <- alpha*fl32(A)*X + beta*Y for nvec column-major vectors in HBM, with
         the float copy of the values (``spx.gpu.values_f32``); the arguments of ``hip_matmat_kernel``."""
-        L = lib()
-        L.spx_hip_matmat_kernel_f32.restype = C.c_int
-        L.spx_hip_matmat_kernel_f32.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
-        rc = L.spx_hip_matmat_kernel_f32(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
-        if rc != SPX_SUCCESS:
-            raise SpxError("spx_hip_matmat_kernel_f32 failed (see stderr)")
+        self._hip_matmat("spx_hip_matmat_kernel_f32", alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream)
 
     def matmat_group_f32(self):
         """``spx_hip_matmat_group_f32``: vectors one pass of ``matmat_f32`` over the stream serves (1: one float
@@ -469,13 +478,7 @@ class Matrix:
         """``spx_hip_matmat_rm_kernel``: Y <- alpha*A*X + beta*Y for nvec vectors of row-major (interleaved)
         blocks in HBM (entry (i, j) of X at x_ptr + 8*(i*ldx + j), of Y at y_ptr + 8*(i*ldy + j)).  General
         tunes only."""
-        L = lib()
-        L.spx_hip_matmat_rm_kernel.restype = C.c_int
-        L.spx_hip_matmat_rm_kernel.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                               C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
-        rc = L.spx_hip_matmat_rm_kernel(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
-        if rc != SPX_SUCCESS:
-            raise SpxError("spx_hip_matmat_rm_kernel failed (see stderr)")
+        self._hip_matmat("spx_hip_matmat_rm_kernel", alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream)
 
     def matmat_rm_group(self):
         """``spx_hip_matmat_rm_group``: vectors one pass of the row-major product serves (8, 4, 2 or 1;
@@ -490,57 +493,19 @@ class Matrix:
         X of shape (ncols, nvec), Y of shape (nrows, nvec), each column one vector, stride(1) == 1 and
         stride(0) >= nvec the leading dimension.  General tunes only.  `stream`: a torch stream (default: the
         current one of Y's device).  Returns Y."""
-        return self._matmat_rm(self.hip_matmat_rm_kernel, alpha, X, beta, Y, stream)
-
-    def _matmat_rm(self, kernel, alpha, X, beta, Y, stream):
-        import torch
-        pairs = (("X", X, self.ncols), ("Y", Y, self.nrows))
-        for name, t, n in pairs:
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("%s must be a torch tensor" % name)
-            if t.dtype != torch.float64:
-                raise ValueError("%s must be float64, not %s" % (name, t.dtype))
-            if t.dim() != 2 or t.shape[0] != n:
-                raise ValueError("%s must have the shape (%d, nvec), not %s" % (name, n, tuple(t.shape)))
-        if X.shape[1] != Y.shape[1]:
-            raise ValueError("X holds %d vectors, Y %d" % (X.shape[1], Y.shape[1]))
-        for name, t, n in pairs:
-            if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
-                raise ValueError("%s needs stride(1) == 1, not %d" % (name, t.stride(1)))
-            if t.shape[0] > 1 and t.shape[1] > 0 and t.stride(0) < t.shape[1]:
-                raise ValueError("%s: stride(0) %d is below the number of vectors %d" % (name, t.stride(0), t.shape[1]))
-        for name, t, n in pairs:
-            if t.device.type != "cuda":
-                raise ValueError("%s must live on the matrix' HIP device, not on %s" % (name, t.device))
-        if X.device != Y.device:
-            raise ValueError("X and Y live on different devices (%s, %s)" % (X.device, Y.device))
-        inf = self.info()
-        if inf.on_device and X.device.index != inf.device:
-            raise ValueError("the matrix lives on cuda:%d, the tensors on %s" % (inf.device, X.device))
-        nvec = int(X.shape[1])
-        ldx = max(int(X.stride(0)), nvec) if self.ncols > 1 else max(nvec, 1)
-        ldy = max(int(Y.stride(0)), nvec) if self.nrows > 1 else max(nvec, 1)
-        st = stream if stream is not None else torch.cuda.current_stream(Y.device)
-        kernel(alpha, X.data_ptr(), ldx, nvec, beta, Y.data_ptr(), ldy, st.cuda_stream)
-        return Y
+        return self._matmat(self.hip_matmat_rm_kernel, alpha, X, beta, Y, stream, rm=True)
 
     def hip_matmat_rm_kernel_f32(self, alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream=0):
         """``spx_hip_matmat_rm_kernel_f32``: Y <- alpha*fl32(A)*X + beta*Y for nvec vectors of row-major
         (interleaved) blocks in HBM, with the float copy of the values (``spx.gpu.values_f32``); the arguments of
         ``hip_matmat_rm_kernel``.  General tunes only."""
-        L = lib()
-        L.spx_hip_matmat_rm_kernel_f32.restype = C.c_int
-        L.spx_hip_matmat_rm_kernel_f32.argtypes = [C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                                   C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]
-        rc = L.spx_hip_matmat_rm_kernel_f32(alpha, self.handle, nvec, x_ptr, ldx, beta, y_ptr, ldy, stream)
-        if rc != SPX_SUCCESS:
-            raise SpxError("spx_hip_matmat_rm_kernel_f32 failed (see stderr)")
+        self._hip_matmat("spx_hip_matmat_rm_kernel_f32", alpha, x_ptr, ldx, nvec, beta, y_ptr, ldy, stream)
 
     def matmat_rm_f32(self, alpha, X, beta, Y, stream=None):
         """Y <- alpha*fl32(A)*X + beta*Y: ``matmat_rm`` (its tensors, checks and return value) with the float
         copy of the values.  General tunes only; SpxError on a matrix without a float copy.  The group is
         ``matmat_rm_group()``."""
-        return self._matmat_rm(self.hip_matmat_rm_kernel_f32, alpha, X, beta, Y, stream)
+        return self._matmat(self.hip_matmat_rm_kernel_f32, alpha, X, beta, Y, stream, rm=True)
 
     def info(self):
         inf = HipInfo()

@@ -2369,9 +2369,25 @@ try {
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
-// spx_hip_matmat_kernel, and with `f32` spx_hip_matmat_kernel_f32: one set of checks, then the product that
-// reads the doubles or the one that reads the float copy (refused where there is none: no fp64 fallback)
-static spx_error_t matmat_checked(bool f32, spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
+// one block of a multi-vector product: `runs` runs of `len` doubles, `stride` doubles from one run's start to the
+// next's (column-major: nvec runs of the vector length at the leading dimension; row-major: a run of nvec per
+// matrix row or column)
+struct BlockShape {
+    size_t runs, len, stride;
+};
+
+// the bytes from the first element to behind the last; false where that is more than the address space holds
+static bool block_span(const BlockShape &b, size_t &bytes)
+{
+    const size_t limit = SIZE_MAX / sizeof(double);
+    if (b.runs > 1 && b.stride && b.runs - 1 > (limit - b.len) / b.stride) return false;
+    bytes = b.runs ? ((b.runs - 1) * b.stride + b.len) * sizeof(double) : 0;
+    return true;
+}
+
+// The four spx_hip_matmat*_kernel* entries: one set of checks, then the product of the layout (`rm`: row-major blocks)
+// that reads the doubles or (`f32`) the float copy (refused where there is none: no fp64 fallback)
+static spx_error_t matmat_checked(bool rm, bool f32, spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                   const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                   spx_value_t *Y_dev, size_t ldy, void *stream)
 {
@@ -2381,28 +2397,43 @@ static spx_error_t matmat_checked(bool f32, spx_value_t alpha, const spx_matrix_
                    "matrix was tuned with spx.rt.host_only=true: no HIP executor");
         return SPX_FAILURE;
     }
+    if (rm && A->symmetric) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "the row-major multi-vector product serves general tunes only: this matrix was "
+                                      "tuned as a symmetric one (tune block solvers as general, or use "
+                                      "spx_hip_matmat_kernel on column-major blocks)");
+        return SPX_FAILURE;
+    }
+    if (rm && A->dist) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "the row-major multi-vector product does not serve a matrix with an exchange "
+                                      "plan attached (spx_hip_mat_dist_attach)");
+        return SPX_FAILURE;
+    }
     if (nvec == 0) return SPX_SUCCESS;
     if (!X_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid block X"); return SPX_FAILURE; }
     if (!Y_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid block Y"); return SPX_FAILURE; }
     const size_t nr = (size_t) A->nrows, nc = (size_t) A->ncols;
-    if (ldx < nc || ldy < nr) {
-        SETERROR_1(SPX_ERR_DIM, "leading dimension below the vector length (ldx >= ncols, ldy >= nrows)");
+    const BlockShape bx = rm ? BlockShape{nc, nvec, ldx} : BlockShape{nvec, nc, ldx};
+    const BlockShape by = rm ? BlockShape{nr, nvec, ldy} : BlockShape{nvec, nr, ldy};
+    if (ldx < bx.len || ldy < by.len) {
+        SETERROR_1(SPX_ERR_DIM, rm ? "leading dimension below the number of vectors (ldx >= nvec, ldy >= nvec)"
+                                   : "leading dimension below the vector length (ldx >= ncols, ldy >= nrows)");
         return SPX_FAILURE;
     }
     // the address ranges the two blocks span, first element to last, must not meet
-    const size_t limit = SIZE_MAX / sizeof(double);
-    if ((ldx && nvec - 1 > (limit - nc) / ldx) || (ldy && nvec - 1 > (limit - nr) / ldy)) {
+    size_t xbytes, ybytes;
+    if (!block_span(bx, xbytes) || !block_span(by, ybytes)) {
         SETERROR_1(SPX_ERR_ARG_INVALID, "block larger than the address space");
         return SPX_FAILURE;
     }
-    const uintptr_t x0 = (uintptr_t) X_dev, x1 = x0 + ((nvec - 1) * ldx + nc) * sizeof(double);
-    const uintptr_t y0 = (uintptr_t) Y_dev, y1 = y0 + ((nvec - 1) * ldy + nr) * sizeof(double);
+    const uintptr_t x0 = (uintptr_t) X_dev, x1 = x0 + xbytes;
+    const uintptr_t y0 = (uintptr_t) Y_dev, y1 = y0 + ybytes;
     if (x0 < y1 && y0 < x1) {
         SETERROR_1(SPX_ERR_ARG_INVALID, "blocks X and Y overlap");
         return SPX_FAILURE;
     }
     try {
-        (f32 ? device_spmm_f32 : device_spmm)(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
+        (rm ? (f32 ? device_spmm_rm_f32 : device_spmm_rm) : (f32 ? device_spmm_f32 : device_spmm))(
+            A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
     } catch (const FatalError &e) {
         SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
         return SPX_FAILURE;
@@ -2414,14 +2445,14 @@ spx_error_t spx_hip_matmat_kernel(spx_value_t alpha, const spx_matrix_t *A, size
                                   const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                   spx_value_t *Y_dev, size_t ldy, void *stream)
 try {
-    return matmat_checked(false, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
+    return matmat_checked(false, false, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
 spx_error_t spx_hip_matmat_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                       const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                       spx_value_t *Y_dev, size_t ldy, void *stream)
 try {
-    return matmat_checked(true, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
+    return matmat_checked(false, true, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
 int spx_hip_matmat_group(const spx_matrix_t *A)
@@ -2434,69 +2465,18 @@ try {
     return A && A->dev ? device_mv_group_f32(A->dev) : -1;
 } SPX_C_BOUNDARY(return -1;)
 
-// spx_hip_matmat_rm_kernel, and with `f32` spx_hip_matmat_rm_kernel_f32
-static spx_error_t matmat_rm_checked(bool f32, spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
-                                     const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
-                                     spx_value_t *Y_dev, size_t ldy, void *stream)
-{
-    if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return SPX_FAILURE; }
-    if (!A->dev) {
-        SETERROR_1(SPX_ERR_TUNED_MAT,
-                   "matrix was tuned with spx.rt.host_only=true: no HIP executor");
-        return SPX_FAILURE;
-    }
-    if (A->symmetric) {
-        SETERROR_1(SPX_ERR_TUNED_MAT, "the row-major multi-vector product serves general tunes only: this matrix was "
-                                      "tuned as a symmetric one (tune block solvers as general, or use "
-                                      "spx_hip_matmat_kernel on column-major blocks)");
-        return SPX_FAILURE;
-    }
-    if (A->dist) {
-        SETERROR_1(SPX_ERR_TUNED_MAT, "the row-major multi-vector product does not serve a matrix with an exchange "
-                                      "plan attached (spx_hip_mat_dist_attach)");
-        return SPX_FAILURE;
-    }
-    if (nvec == 0) return SPX_SUCCESS;
-    if (!X_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid block X"); return SPX_FAILURE; }
-    if (!Y_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid block Y"); return SPX_FAILURE; }
-    if (ldx < nvec || ldy < nvec) {
-        SETERROR_1(SPX_ERR_DIM, "leading dimension below the number of vectors (ldx >= nvec, ldy >= nvec)");
-        return SPX_FAILURE;
-    }
-    const size_t nr = (size_t) A->nrows, nc = (size_t) A->ncols;
-    // the address ranges the two blocks span, first element to last, must not meet
-    const size_t limit = SIZE_MAX / sizeof(double);
-    if ((nc > 1 && nc - 1 > (limit - nvec) / ldx) || (nr > 1 && nr - 1 > (limit - nvec) / ldy)) {
-        SETERROR_1(SPX_ERR_ARG_INVALID, "block larger than the address space");
-        return SPX_FAILURE;
-    }
-    const uintptr_t x0 = (uintptr_t) X_dev, x1 = x0 + (nc ? ((nc - 1) * ldx + nvec) * sizeof(double) : 0);
-    const uintptr_t y0 = (uintptr_t) Y_dev, y1 = y0 + (nr ? ((nr - 1) * ldy + nvec) * sizeof(double) : 0);
-    if (x0 < y1 && y0 < x1) {
-        SETERROR_1(SPX_ERR_ARG_INVALID, "blocks X and Y overlap");
-        return SPX_FAILURE;
-    }
-    try {
-        (f32 ? device_spmm_rm_f32 : device_spmm_rm)(A->dev, alpha, X_dev, ldx, nvec, beta, Y_dev, ldy, stream);
-    } catch (const FatalError &e) {
-        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
-        return SPX_FAILURE;
-    }
-    return SPX_SUCCESS;
-}
-
 spx_error_t spx_hip_matmat_rm_kernel(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                      const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                      spx_value_t *Y_dev, size_t ldy, void *stream)
 try {
-    return matmat_rm_checked(false, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
+    return matmat_checked(true, false, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
 spx_error_t spx_hip_matmat_rm_kernel_f32(spx_value_t alpha, const spx_matrix_t *A, size_t nvec,
                                          const spx_value_t *X_dev, size_t ldx, spx_value_t beta,
                                          spx_value_t *Y_dev, size_t ldy, void *stream)
 try {
-    return matmat_rm_checked(true, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
+    return matmat_checked(true, true, alpha, A, nvec, X_dev, ldx, beta, Y_dev, ldy, stream);
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
 int spx_hip_matmat_rm_group(const spx_matrix_t *A)

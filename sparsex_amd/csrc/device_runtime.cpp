@@ -902,27 +902,30 @@ static bool mvsym_on(const DeviceMatrix *m)
     return m->has_tiles && m->sym_matmat && m->sym_atomic && !m->wave_tiles && m->carry_mv;
 }
 
+// the widest group (8, 4, 2) whose workgroup fits `budget` without the x windows, which are the launch's business:
+// staged where they fit as well (launch_rowblocks_mv); 1 where none does
+static int widest_group(const DeviceMatrix *m, size_t (*lds_bytes)(const DeviceMatrix *, int, bool), size_t budget)
+{
+    for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
+        if (lds_bytes(m, K, false) <= budget) return K;
+    return 1;
+}
+
 // the widest group whose y tiles fit MV_LDS_BUDGET (from the tune-time settings: row-blocks, waves, tiles per
-// wavefront); 1 where only the single-vector product runs
+// wavefront), or whose K x {slots, y tile} of the largest row-block and slot groups' columns fit MVSYM_LDS_BUDGET;
+// 1 where only the single-vector product runs
 int device_mv_group(const DeviceMatrix *m)
 {
-    if (mvsym_on(m)) {
-        // (K x {slots, y tile} of the largest row-block and the slot groups' columns; the x windows are the launch's
-        // business: staged where they fit as well, launch_rowblocks_mv)
-        for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
-            if (mvsym_lds_bytes(m, K, false) <= MVSYM_LDS_BUDGET) return K;
-        return 1;
-    }
+    if (mvsym_on(m)) return widest_group(m, mvsym_lds_bytes, MVSYM_LDS_BUDGET);
     if (m->has_tiles || !m->carry_mv) return 1;
-    for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
-        if (mv_lds_bytes(m, K, false) <= MV_LDS_BUDGET) return K;
-    return 1;
+    return widest_group(m, mv_lds_bytes, MV_LDS_BUDGET);
 }
 
 static uint32_t mv_n_carry(const DeviceMatrix *m) { return m->n_carry ? m->n_carry : 1u; }
 
 // launch_rowblocks for K >= 2 vectors: the plain stream through the kernels of spmv_mv_kernels.hip; `rm`: for K >= 1
-// vectors of row-major blocks (general streams only: device_spmm_rm) through those of spmv_mvr_kernels.hip
+// vectors of row-major blocks (general streams only: device_spmm_rm) through those of spmv_mvr_kernels.hip -- the
+// same kernel template (csx_spmv_mv_kernel), families, LDS formula and staging rule for both layouts
 // (`f32`, streams with a float twin: the same family, wavefronts, LDS and staging, the kernel that reads the twin --
 // spmv_mv_f32_kernels.hip, spmv_mvr_f32_kernels.hip; csx_spmv_mvsym_kernel has no float form)
 static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &a, size_t ldx, size_t ldy,
@@ -937,18 +940,6 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
     mv.x = a.x; mv.y = a.y; mv.ldx = ldx; mv.ldy = ldy;
     mv.carry = m->carry_mv; mv.n_carry = mv_n_carry(m);
     mv.dvalues = a.dvalues; mv.alpha = a.alpha; mv.beta = a.beta; mv.pass_stride = a.pass_stride;
-    if (rm) {
-        // the same families, LDS formula and staging rule as the column-major launch below; 16-byte loads of x
-        // where every column's K doubles are 16-byte aligned
-        MvrArgs mr{};
-        static_cast<MvArgs &>(mr) = mv;
-        mr.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
-        mr.x16 = ((uintptr_t) a.x % 16u == 0 && (ldx * sizeof(double)) % 16u == 0) ? 1u : 0u;
-        const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
-        (f32 ? launch_spmv_mvr_f32 : launch_spmv_mvr)(family, K, m->waves, blocks, mv_lds_bytes(m, K, mr.stage != 0), stream,
-                                                      mr, xcd_now);
-        return;
-    }
     if (m->has_tiles) {
         // read-once passes (device_mv_group: mvsym_on): the K x windows behind the K x {slots, y tile} where they fit
         MvSymArgs ms{};
@@ -959,11 +950,19 @@ static void launch_rowblocks_mv(const DeviceMatrix *m, int K, const KernelArgs &
         launch_spmv_mvsym(K, lds > MVSYM_LDS_FEW ? MAX_WAVES_PER_BLOCK : m->waves, blocks, lds, stream, ms, xcd_now);
         return;
     }
-    // the K x windows in LDS where they fit next to the tiles; else SPX_PASS_GATHER_LDS gathers through L2
+    // the x windows in LDS where they fit next to the tiles; else SPX_PASS_GATHER_LDS gathers through L2
     mv.stage = m->mv_xwin && mv_lds_bytes(m, K, true) <= MV_LDS_BUDGET ? 1u : 0u;
+    const size_t lds = mv_lds_bytes(m, K, mv.stage != 0);
     const MvFamily family = m->wave_tiles && !m->accum ? MvFamily::det : m->accum ? MvFamily::accum : MvFamily::plain;
-    (f32 ? launch_spmv_mv_f32 : launch_spmv_mv)(family, K, m->waves, blocks, mv_lds_bytes(m, K, mv.stage != 0), stream, mv,
-                                                xcd_now);
+    if (rm) {
+        // 16-byte loads of x where every column's K doubles are 16-byte aligned
+        MvrArgs mr{};
+        static_cast<MvArgs &>(mr) = mv;
+        mr.x16 = ((uintptr_t) a.x % 16u == 0 && (ldx * sizeof(double)) % 16u == 0) ? 1u : 0u;
+        (f32 ? launch_spmv_mvr_f32 : launch_spmv_mvr)(family, K, m->waves, blocks, lds, stream, mr, xcd_now);
+    } else {
+        (f32 ? launch_spmv_mv_f32 : launch_spmv_mv)(family, K, m->waves, blocks, lds, stream, mv, xcd_now);
+    }
 }
 
 // Y <- alpha*A*X + beta*Y for K vectors (column-major: vector j of X at X + j * ldx, of Y at Y + j * ldy) in one
@@ -1047,19 +1046,27 @@ static void device_product(DeviceMatrix *m, int K, double alpha, const double *X
     HIP_CHECK(hipGetLastError());
 }
 
+// nvec vectors in groups of the widest K = G, then 4 / 2 / 1 for the remainder, every group one device_product.
+// Group j0 starts at X + j0 * ldx, Y + j0 * ldy in column-major blocks, at X + j0, Y + j0 in row-major ones (`rm`).
+static void spmm_groups(DeviceMatrix *m, int G, bool f32, bool rm, double alpha, const double *X, size_t ldx, size_t nvec,
+                        double beta, double *Y, size_t ldy, void *stream_)
+{
+    const size_t xstep = rm ? 1 : ldx, ystep = rm ? 1 : ldy;
+    for (size_t j = 0; j < nvec;) {
+        int K = G;
+        while (K > 1 && (size_t) K > nvec - j) K /= 2;
+        device_product(m, K, alpha, X + j * xstep, ldx, beta, Y + j * ystep, ldy, stream_, nullptr, f32, rm);
+        j += (size_t) K;
+    }
+}
+
 // Y <- alpha*A*X + beta*Y for nvec column-major vectors: groups of K vectors served by one pass over the plain
 // stream.  Streams with symmetric tiles or read-once segments (but under spx.gpu.sym_matmat), and a last vector on
 // its own, run the single-vector product: exact, column by column.
 void device_spmm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
                  size_t ldy, void *stream_)
 {
-    const int G = device_mv_group(m);
-    for (size_t j = 0; j < nvec;) {
-        int K = G;
-        while (K > 1 && (size_t) K > nvec - j) K /= 2;
-        device_product(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_, nullptr);
-        j += (size_t) K;
-    }
+    spmm_groups(m, device_mv_group(m), false, false, alpha, X, ldx, nvec, beta, Y, ldy, stream_);
 }
 
 // the group of device_spmm_f32: device_mv_group's where the plain K-vector kernels run (general streams, symmetric
@@ -1078,13 +1085,7 @@ void device_spmm_f32(DeviceMatrix *m, double alpha, const double *X, size_t ldx,
                      size_t ldy, void *stream_)
 {
     need_values_f32(m);
-    const int G = device_mv_group_f32(m);
-    for (size_t j = 0; j < nvec;) {
-        int K = G;
-        while (K > 1 && (size_t) K > nvec - j) K /= 2;
-        device_product(m, K, alpha, X + j * ldx, ldx, beta, Y + j * ldy, ldy, stream_, nullptr, true);
-        j += (size_t) K;
-    }
+    spmm_groups(m, device_mv_group_f32(m), true, false, alpha, X, ldx, nvec, beta, Y, ldy, stream_);
 }
 
 // the widest group of the row-major product: the budget and the formula of device_mv_group for general streams
@@ -1093,40 +1094,31 @@ void device_spmm_f32(DeviceMatrix *m, double alpha, const double *X, size_t ldx,
 int device_mv_group_rm(const DeviceMatrix *m)
 {
     if (m->symmetric || m->has_tiles || !m->carry_mv) return 0;
-    for (int K = MV_MAX_GROUP; K >= 2; K /= 2)
-        if (mv_lds_bytes(m, K, false) <= MV_LDS_BUDGET) return K;
-    return 1;
+    return widest_group(m, mv_lds_bytes, MV_LDS_BUDGET);
 }
 
 // Y <- alpha*A*X + beta*Y for nvec vectors of row-major blocks (entry (i, j) of X at X[i * ldx + j], of Y at
-// Y[i * ldy + j]): groups of the widest K that fits, then 4 / 2 / 1 for the remainder, group j0 on X + j0, Y + j0.
+// Y[i * ldy + j]); `f32`: Y <- alpha*fl32(A)*X + beta*Y through the kernels that read the float twin, the same groups.
 // General streams only: the single-vector kernels cannot read a strided x, so there is no per-column fallback.
+static void spmm_rm(DeviceMatrix *m, bool f32, double alpha, const double *X, size_t ldx, size_t nvec, double beta,
+                    double *Y, size_t ldy, void *stream_)
+{
+    const int G = device_mv_group_rm(m);
+    if (G < 1) throw FatalError("the row-major multi-vector product serves general (non-symmetric) tunes only");
+    if (f32) need_values_f32(m);
+    spmm_groups(m, G, f32, true, alpha, X, ldx, nvec, beta, Y, ldy, stream_);
+}
+
 void device_spmm_rm(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
                     size_t ldy, void *stream_)
 {
-    const int G = device_mv_group_rm(m);
-    if (G < 1) throw FatalError("the row-major multi-vector product serves general (non-symmetric) tunes only");
-    for (size_t j = 0; j < nvec;) {
-        int K = G;
-        while (K > 1 && (size_t) K > nvec - j) K /= 2;
-        device_product(m, K, alpha, X + j, ldx, beta, Y + j, ldy, stream_, nullptr, false, true);
-        j += (size_t) K;
-    }
+    spmm_rm(m, false, alpha, X, ldx, nvec, beta, Y, ldy, stream_);
 }
 
-// ... through the kernels that read the float twin: Y <- alpha*fl32(A)*X + beta*Y, the same groups
 void device_spmm_rm_f32(DeviceMatrix *m, double alpha, const double *X, size_t ldx, size_t nvec, double beta, double *Y,
                         size_t ldy, void *stream_)
 {
-    const int G = device_mv_group_rm(m);
-    if (G < 1) throw FatalError("the row-major multi-vector product serves general (non-symmetric) tunes only");
-    need_values_f32(m);
-    for (size_t j = 0; j < nvec;) {
-        int K = G;
-        while (K > 1 && (size_t) K > nvec - j) K /= 2;
-        device_product(m, K, alpha, X + j, ldx, beta, Y + j, ldy, stream_, nullptr, true, true);
-        j += (size_t) K;
-    }
+    spmm_rm(m, true, alpha, X, ldx, nvec, beta, Y, ldy, stream_);
 }
 
 // ---- the product in K launches over consecutive parts of the row-blocks ---------------------------

@@ -128,10 +128,12 @@ struct MvArgs : StreamArgs {
     uint32_t pass_stride;
     uint32_t stage;            // 1: the K x windows of a row-block are staged in LDS behind the K y tiles
 };
+// the families of csx_spmv_mv_kernel<Args, V, family, K, waves> (spmv_mv_instances.hpp): one kernel template for
+// both layouts (Args: MvArgs, or MvrArgs below) and both value types (V: double, or float for the twin)
 enum class MvFamily {
-    plain,     // csx_spmv_mv_kernel: K y tiles per workgroup
-    accum,     // csx_spmv_mv_accum_kernel: column slices in one launch, tiles added with atomics
-    det,       // csx_spmv_mv_det_kernel: K y tiles per wavefront, summed in wavefront order
+    plain,     // K y tiles per workgroup
+    accum,     // column slices in one launch, tiles added with atomics
+    det,       // K y tiles per wavefront, summed in wavefront order
 };
 void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
                     const XcdSplit &xs);

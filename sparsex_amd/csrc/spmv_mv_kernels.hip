@@ -12,77 +12,20 @@
 // DET (spx.gpu.deterministic, or the launch tuner's tile per wavefront): a copy of the K tiles per
 // wavefront, the passes taken by the wavefronts in the order and pairs of csx_spmv_det_kernel, the
 // copies summed in wavefront order: every column is bit-identical to the single-vector product.
-// (mv_body, the body of the kernels below and of their float forms in spmv_mv_f32_kernels.hip: spmv_mv_device.hpp)
-#include "spmv_mv_device.hpp"
+// (mv_body: spmv_mv_device.hpp; the kernel template over it, csx_spmv_mv_kernel<MvArgs, double, family, K, waves>,
+// and the table of its instances: spmv_mv_instances.hpp)
+#include "spmv_mv_instances.hpp"
 
 namespace spx {
 
-template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES)
-void csx_spmv_mv_kernel(MvArgs a, XcdSplit xs)
-{
-    extern __shared__ double lds_dyn[];      // K y tiles, then the K x windows
-    mv_body<K, WAVES, false, false>(a, xs, lds_dyn);
-}
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES)
-void csx_spmv_mv_accum_kernel(MvArgs a, XcdSplit xs)
-{
-    extern __shared__ double lds_dyn[];
-    mv_body<K, WAVES, true, false>(a, xs, lds_dyn);
-}
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES)
-void csx_spmv_mv_det_kernel(MvArgs a, XcdSplit xs)
-{
-    extern __shared__ double lds_dyn[];      // K y tiles per wavefront, then the K x windows
-    mv_body<K, WAVES, false, true>(a, xs, lds_dyn);
-}
-
-// ---- launchers ------------------------------------------------------------------------------
-
-typedef void (*MvKernel)(MvArgs, XcdSplit);
-
-template <int K, int WAVES>
-static MvKernel mv_kernel(MvFamily family)
-{
-    switch (family) {
-    case MvFamily::accum: return csx_spmv_mv_accum_kernel<K, WAVES>;
-    case MvFamily::det: return csx_spmv_mv_det_kernel<K, WAVES>;
-    case MvFamily::plain: break;
-    }
-    return csx_spmv_mv_kernel<K, WAVES>;
-}
-
-template <int K>
-static MvKernel mv_kernel_w(MvFamily family, int waves)
-{
-    return waves == 2 ? mv_kernel<K, 2>(family) : waves == 8 ? mv_kernel<K, 8>(family) : mv_kernel<K, 4>(family);
-}
-
-static MvKernel mv_kernel_kw(MvFamily family, int K, int waves)
-{
-    return K == 8 ? mv_kernel_w<8>(family, waves) : K == 4 ? mv_kernel_w<4>(family, waves) : mv_kernel_w<2>(family, waves);
-}
+using Instances = MvInstances<MvArgs, double, 2, 4, 8>;
 
 void launch_spmv_mv(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvArgs &a,
                     const XcdSplit &xs)
 {
-    const int w = (waves == 2 || waves == 8) ? waves : 4;
-    hipLaunchKernelGGL(mv_kernel_kw(family, K, w), dim3(blocks), dim3(64 * w), lds_bytes, static_cast<hipStream_t>(stream),
-                       a, xs);
+    Instances::launch(family, K, waves, blocks, lds_bytes, stream, a, xs);
 }
 
-void spmv_mv_allow_lds(size_t bytes)
-{
-    const int b = (int) bytes;
-    for (MvFamily f : {MvFamily::plain, MvFamily::accum, MvFamily::det})
-        for (int K : {2, 4, 8})
-            for (int w : {2, 4, 8})
-                (void) hipFuncSetAttribute(reinterpret_cast<const void *>(mv_kernel_kw(f, K, w)),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, b);
-}
+void spmv_mv_allow_lds(size_t bytes) { Instances::allow_lds(bytes); }
 
 }  // namespace spx

@@ -1,15 +1,16 @@
 // spmv_mvr_device.hpp -- device code of the multi-vector product on ROW-MAJOR (interleaved) blocks,
-// csx_spmv_mvr_kernel (spmv_mvr_kernels.hip): the K-vector composition of the pieces of spmv_device.hpp for
-// an x whose entry (column c, vector j) lies at x[c * ldx + j].  The K doubles a lane needs of column c are
-// contiguous -- one or two cache lines for K = 8 where the column-major composition gathers K of them.
+// csx_spmv_mv_kernel<MvrArgs, ...> (spmv_mvr_kernels.hip, spmv_mvr_f32_kernels.hip): the K-vector composition of
+// the pieces of spmv_device.hpp for an x whose entry (column c, vector j) lies at x[c * ldx + j].  The K doubles a
+// lane needs of column c are contiguous -- one or two cache lines for K = 8 where the column-major composition
+// gathers K of them.
 //
 // Overloads unit_passes of spmv_device.hpp on the argument struct, so that run_units, run_pass and run_pair
 // -- the pass kinds, widths and the pairing of two passes of one shape -- are the ones every interpreter
-// kernel uses.
+// kernel uses; and stage_xwin and write_rows of spmv_mv_device.hpp, so that the body around them, mv_body, is the
+// column-major kernels'.
 #pragma once
 
-#include "spmv_device.hpp"
-#include "spmv_launch.hpp"
+#include "spmv_mv_device.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -134,84 +135,33 @@ __device__ __forceinline__ void unit_passes(const MvrArgs &a, const SpxRowBlock 
     }
 }
 
-// ---- the body of csx_spmv_mvr_kernel and its kin (spmv_mvr_kernels.hip, spmv_mvr_f32_kernels.hip) ----------------
+// ---- the two layout-dependent pieces of mv_body (spmv_mv_device.hpp) for row-major blocks ----------------------
 
-// One workgroup owns one row-block: LDS holds COPIES x K y tiles (copy c, vector j at (c * K + j) * n_rows),
-// then the x window (xwin_len x K doubles, row-major) where it is staged.
-// V: the type of the stream's values (float: a.values points at the float twin, spx.gpu.values_f32); x, the
-// window, the tiles, products, sums and the write-out are fp64 whatever V is.
-template <int K, int WAVES, bool ACCUM, bool DET, class V = double>
-__device__ __forceinline__ void mvr_body(const MvrArgs &a, const XcdSplit &xs, double *lds)
+// the x window: rows xwin_base .. xwin_base + xwin_len - 1 of X, K doubles of each (entry (i, j) at win[i * K + j]):
+// one run where ldx == K
+template <int K, int BLOCK_THREADS>
+__device__ __forceinline__ void stage_xwin(const MvrArgs &a, const SpxRowBlock &rb, double *win)
 {
-    constexpr int BLOCK_THREADS = 64 * WAVES;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t xcd = blockIdx.x & 7u;
-    const uint32_t rb_idx = xs.first[xcd] + (blockIdx.x >> 3);
-    if (rb_idx >= xs.first[xcd + 1u]) return;
+    const int xk = (int) rb.xwin_len * K;
+    const double *xw = a.x + (size_t) rb.xwin_base * a.ldx;
+    for (int e = threadIdx.x; e < xk; e += BLOCK_THREADS) win[e] = xw[(size_t) (e / K) * a.ldx + (e % K)];
+}
 
-    const SpxPass *passes = a.passes + (size_t) rb_idx * a.pass_stride;
-    const SpxRowBlock rb = a.rbs[rb_idx];
-    SpxPass p0 = passes[wave];
-    SpxPass p1 = passes[wave + WAVES];                   // (the table is padded by one stride)
-    const int n_rows = rb.n_rows;
-    constexpr int COPIES = DET ? WAVES : 1;
-    const int tiles = K * n_rows;                        // doubles per copy
-    double *tile = lds + (DET ? wave * tiles : 0);
-    for (int i = threadIdx.x; i < COPIES * tiles; i += BLOCK_THREADS) lds[i] = 0.0;
-    double *win = lds + COPIES * tiles;
-    if (a.stage) {
-        // rows xwin_base .. xwin_base + xwin_len - 1 of X, K doubles of each: one run where ldx == K
-        const int xk = (int) rb.xwin_len * K;
-        const double *xw = a.x + (size_t) rb.xwin_base * a.ldx;
-        for (int e = threadIdx.x; e < xk; e += BLOCK_THREADS) win[e] = xw[(size_t) (e / K) * a.ldx + (e % K)];
-    }
-    __syncthreads();
-
-    // wave w takes passes w, w + WAVES, ..., two at a time when they have the same shape
-    const int n_pass = rb.n_pass;
-    for (int t = wave; t < n_pass; t += 2 * WAVES) {
-        const bool two = t + WAVES < n_pass;
-        if (two) {
-            if (same_shape(p0, p1)) {
-                run_pair<K, V>(a, rb, {p0, p1}, tile, win, lane);
-            } else {
-                run_pass<K, V>(a, rb, p0, tile, win, lane);
-                run_pass<K, V>(a, rb, p1, tile, win, lane);
-            }
-        } else {
-            run_pass<K, V>(a, rb, p0, tile, win, lane);
-        }
-        if (t + 2 * WAVES < n_pass) {
-            p0 = passes[t + 2 * WAVES];
-            p1 = passes[t + 3 * WAVES];
-        }
-    }
-    __syncthreads();
-    if (DET) {
-        // the wavefronts' copies, summed in wavefront order into the first one
-        for (int i = threadIdx.x; i < tiles; i += BLOCK_THREADS) {
-            double t = lds[i];
-#pragma unroll
-            for (int w = 1; w < COPIES; ++w) t += lds[w * tiles + i];
-            lds[i] = t;
-        }
-        __syncthreads();
-        tile = lds;
-    }
-
-    // ---- write the owned rows: entry e of the row-block's n_rows x K piece of Y, in memory order ----------
-    if (rb.flags & SPX_RB_SHARED) {
-        if (threadIdx.x < K) a.carry[(size_t) threadIdx.x * a.n_carry + rb.carry_slot] = tile[threadIdx.x * n_rows];
-    } else if (ACCUM) {
+// the owned rows: entry e of the row-block's n_rows x K piece of Y, in memory order (the tiles are vector-major:
+// transposed here); no diagonal term (general streams only)
+template <int K, int BLOCK_THREADS, bool ACCUM, class V>
+__device__ __forceinline__ void write_rows(const MvrArgs &a, uint32_t row0, int n_rows, const double *tile)
+{
+    const int tiles = K * n_rows;
+    if (ACCUM) {
         for (int e = threadIdx.x; e < tiles; e += BLOCK_THREADS) {
             const int i = e / K, j = e % K;
-            atomicAdd(&a.y[((size_t) rb.row0 + i) * a.ldy + j], a.alpha * tile[j * n_rows + i]);
+            atomicAdd(&a.y[((size_t) row0 + i) * a.ldy + j], a.alpha * tile[j * n_rows + i]);
         }
     } else {
         for (int e = threadIdx.x; e < tiles; e += BLOCK_THREADS) {
             const int i = e / K, j = e % K;
-            double *yp = a.y + ((size_t) rb.row0 + i) * a.ldy + j;
+            double *yp = a.y + ((size_t) row0 + i) * a.ldy + j;
             double t = tile[j * n_rows + i];
             t *= a.alpha;
             if (a.beta != 0.0) t += a.beta * *yp;

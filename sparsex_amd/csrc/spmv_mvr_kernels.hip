@@ -3,7 +3,7 @@
 // the stream, K = 1, 2, 4 or 8 (one vector too: a remainder vector of such a block is still strided, which the
 // single-vector kernels cannot read).  The host side is device_spmm_rm (device_runtime.cpp).
 //
-// mv_body of spmv_mv_kernels.hip with the K-vector composition of spmv_mvr_device.hpp: the same row-blocks,
+// The kernel of spmv_mv_kernels.hip with the K-vector composition of spmv_mvr_device.hpp: the same row-blocks,
 // pass order and pairing, K-wide carry and LDS budget, over the PLAIN stream (passes, descs) of a general
 // tune.  What differs is where x and y lie: a lane loads the K contiguous doubles of each of its columns, the
 // staged x window is one copy of xwin_len consecutive rows of X, and the write-out walks the row-block's
@@ -18,41 +18,15 @@
 //
 // DET: as in spmv_mv_kernels.hip -- a copy of the K tiles per wavefront, summed in wavefront order: every
 // column is bit-identical to the single-vector product.
+// (mv_body: spmv_mv_device.hpp; the kernel template over it, csx_spmv_mv_kernel<MvrArgs, double, family, K, waves>,
+// and the table of its instances: spmv_mv_instances.hpp)
 #include "spmv_mvr_device.hpp"
-#include "spmv_launch.hpp"
-
-#include <hip/hip_runtime.h>
+#include "spmv_mv_instances.hpp"
 
 #include <cstddef>
 #include <cstdint>
 
 namespace spx {
-
-// (mvr_body, the body of the kernels below and of their float forms in spmv_mvr_f32_kernels.hip: spmv_mvr_device.hpp)
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES)
-void csx_spmv_mvr_kernel(MvrArgs a, XcdSplit xs)
-{
-    extern __shared__ double lds_dyn[];      // K y tiles, then the x window
-    mvr_body<K, WAVES, false, false>(a, xs, lds_dyn);
-}
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES)
-void csx_spmv_mvr_accum_kernel(MvrArgs a, XcdSplit xs)
-{
-    extern __shared__ double lds_dyn[];
-    mvr_body<K, WAVES, true, false>(a, xs, lds_dyn);
-}
-
-template <int K, int WAVES>
-__global__ __launch_bounds__(64 * WAVES)
-void csx_spmv_mvr_det_kernel(MvrArgs a, XcdSplit xs)
-{
-    extern __shared__ double lds_dyn[];      // K y tiles per wavefront, then the x window
-    mvr_body<K, WAVES, false, true>(a, xs, lds_dyn);
-}
 
 // ---- the steps around the row-block launches, interleaved forms of csx_scale_kernel and csx_fixup_kernel ----
 
@@ -83,48 +57,15 @@ __global__ void csx_fixup_rm_kernel(const SpxSharedRow *shared, uint32_t n_share
 
 // ---- launchers ------------------------------------------------------------------------------
 
-typedef void (*MvrKernel)(MvrArgs, XcdSplit);
-
-template <int K, int WAVES>
-static MvrKernel mvr_kernel(MvFamily family)
-{
-    switch (family) {
-    case MvFamily::accum: return csx_spmv_mvr_accum_kernel<K, WAVES>;
-    case MvFamily::det: return csx_spmv_mvr_det_kernel<K, WAVES>;
-    case MvFamily::plain: break;
-    }
-    return csx_spmv_mvr_kernel<K, WAVES>;
-}
-
-template <int K>
-static MvrKernel mvr_kernel_w(MvFamily family, int waves)
-{
-    return waves == 2 ? mvr_kernel<K, 2>(family) : waves == 8 ? mvr_kernel<K, 8>(family) : mvr_kernel<K, 4>(family);
-}
-
-static MvrKernel mvr_kernel_kw(MvFamily family, int K, int waves)
-{
-    return K == 8 ? mvr_kernel_w<8>(family, waves) : K == 4 ? mvr_kernel_w<4>(family, waves)
-         : K == 2 ? mvr_kernel_w<2>(family, waves) : mvr_kernel_w<1>(family, waves);
-}
+using Instances = MvInstances<MvrArgs, double, 1, 2, 4, 8>;
 
 void launch_spmv_mvr(MvFamily family, int K, int waves, unsigned blocks, size_t lds_bytes, void *stream, const MvrArgs &a,
                      const XcdSplit &xs)
 {
-    const int w = (waves == 2 || waves == 8) ? waves : 4;
-    hipLaunchKernelGGL(mvr_kernel_kw(family, K, w), dim3(blocks), dim3(64 * w), lds_bytes, static_cast<hipStream_t>(stream),
-                       a, xs);
+    Instances::launch(family, K, waves, blocks, lds_bytes, stream, a, xs);
 }
 
-void spmv_mvr_allow_lds(size_t bytes)
-{
-    const int b = (int) bytes;
-    for (MvFamily f : {MvFamily::plain, MvFamily::accum, MvFamily::det})
-        for (int K : {1, 2, 4, 8})
-            for (int w : {2, 4, 8})
-                (void) hipFuncSetAttribute(reinterpret_cast<const void *>(mvr_kernel_kw(f, K, w)),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, b);
-}
+void spmv_mvr_allow_lds(size_t bytes) { Instances::allow_lds(bytes); }
 
 void launch_scale_rm(void *stream, int nvec, double *y, size_t ldy, size_t lo, size_t hi, double beta)
 {

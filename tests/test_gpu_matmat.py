@@ -119,6 +119,10 @@ def test_bad_arguments_fail(tuned):
         A.hip_matmat_kernel(1.0, base, n, 2, 0.0, base + 16 * n, n - 1, s)
     with pytest.raises(sx.SpxError):                      # NULL
         A.hip_matmat_kernel(1.0, 0, n, 2, 0.0, base + 16 * n, n, s)
+    with pytest.raises(sx.SpxError):                      # three vectors 2^62 doubles apart: past the address space
+        A.hip_matmat_kernel(1.0, base, 1 << 62, 3, 0.0, base + 16 * n, n, s)
+    with pytest.raises(sx.SpxError):                      # ... of Y
+        A.hip_matmat_kernel(1.0, base, n, 3, 0.0, base + 24 * n, 1 << 62, s)
     torch.cuda.synchronize()
     assert not buf.any()
     # (adjacent, not overlapping: fine)

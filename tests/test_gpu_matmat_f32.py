@@ -1,5 +1,5 @@
 """The multi-vector product with the float copy of the values on column-major blocks, spx_hip_matmat_kernel_f32 /
-Matrix.matmat_f32, on the GPU: csx_spmv_mv_f32_kernel, csx_spmv_mv_accum_f32_kernel and csx_spmv_mv_det_f32_kernel
+Matrix.matmat_f32, on the GPU: the plain, accum and det families of csx_spmv_mv_kernel<MvArgs, float, ...>
 (spmv_mv_f32_kernels.hip) on handles tuned with spx.gpu.values_f32.
 
 The reference of every result is matmat_cases.check_y_rect -- the project's fp64 bound and its relative 1e-6

@@ -336,6 +336,10 @@ def test_bad_arguments_fail(tuned):
         A.hip_matmat_rm_kernel(1.0, 0, 2, 2, 0.0, base + 16 * n, 2, s)
     with pytest.raises(sx.SpxError):                      # NULL Y
         A.hip_matmat_rm_kernel(1.0, base, 2, 2, 0.0, 0, 2, s)
+    with pytest.raises(sx.SpxError):                      # rows 2^62 doubles apart: past the address space
+        A.hip_matmat_rm_kernel(1.0, base, 1 << 62, 2, 0.0, base + 16 * n, 2, s)
+    with pytest.raises(sx.SpxError):                      # ... of Y
+        A.hip_matmat_rm_kernel(1.0, base, 2, 2, 0.0, base + 16 * n, 1 << 62, s)
     torch.cuda.synchronize()
     assert not buf.any()
     # (adjacent, not overlapping: fine)

@@ -1,6 +1,6 @@
 """The multi-vector product with the float copy of the values on row-major (interleaved) blocks,
-spx_hip_matmat_rm_kernel_f32 / Matrix.matmat_rm_f32, on the GPU: csx_spmv_mvr_f32_kernel,
-csx_spmv_mvr_accum_f32_kernel and csx_spmv_mvr_det_f32_kernel (spmv_mvr_f32_kernels.hip) on general handles tuned
+spx_hip_matmat_rm_kernel_f32 / Matrix.matmat_rm_f32, on the GPU: the plain, accum and det
+families of csx_spmv_mv_kernel<MvrArgs, float, ...> (spmv_mvr_f32_kernels.hip) on general handles tuned
 with spx.gpu.values_f32=true.  Entry (i, j) of X at X[i * ldx + j], of Y at Y[i * ldy + j].
 
 The reference of every column is matmat_cases.check_y_rect on the CSR arrays with
