@@ -422,6 +422,10 @@ spx_error_t spx_hip_vec_mul_elem(const spx_hip_vec_t *v1, const spx_hip_vec_t *v
 /* v2 <- 1 / v1 elementwise (IEEE division), if_zero where v1 is +-0; v2 may be v1.  With spx_hip_mat_get_diag_vec
  * in front of it: the Jacobi preconditioner of the matrix (rows without a diagonal entry get if_zero). */
 spx_error_t spx_hip_vec_reciprocal(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, spx_value_t if_zero, void *stream);
+/* v2 <- 1 / sqrt(v1) elementwise (one IEEE square root, one IEEE division), if_zero where v1 is +-0; v2 may be v1.
+ * Enqueue only, legal during stream capture.  Behind spx_hip_mat_norms(SPX_HIP_NORM_MAX_ABS): the factors of one
+ * Ruiz equilibration sweep for spx_hip_mat_scale. */
+spx_error_t spx_hip_vec_rsqrt(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, spx_value_t if_zero, void *stream);
 /* One preconditioned CG update in one pass over the vectors, minv any diagonal preconditioner:
  *   a = *rz_dev / *pap_dev (0 if *pap_dev == 0);  x += a*p;  r -= a*ap;
  *   z_i = minv_i * r_i (one rounded multiplication; z is not stored);
@@ -804,6 +808,60 @@ typedef struct {
     uint64_t plan_bytes;          /* HBM the plan occupies (0 on host-only and symmetric matrices)           */
 } spx_hip_diag_plan_t;
 spx_error_t spx_hip_mat_diag_plan_get(const spx_matrix_t *A, spx_hip_diag_plan_t *plan);
+
+/* Row and column norms and in-place diagonal scaling of a tuned matrix, A <- D_r * A * D_c: what a solver does
+ * to a matrix before it iterates (PETSc: MatGetRowMaxAbs, MatGetColumnNorms, MatNorm, MatDiagonalScale), in ONE
+ * pass over the stream where it lies -- no plan, no second copy of the matrix, no host round trip.  GENERAL tunes
+ * (whole matrices, row slices, every spx.gpu.col_phases setting, unit windows, spx.gpu.deterministic, reordered
+ * matrices, with or without the float copy of the values).
+ *
+ *  Vectors
+ *  - They use the numbering of the products' vectors: the tuned one under SPX_MAT_REORDER / spx.rt.dist_reorder.
+ *  - `rows` and `dr` hold nrows doubles, `cols` and `dc` hold ncols doubles; 8-byte aligned.  The _dev pointers
+ *    lie in HBM of the matrix' device, the others in host memory.
+ *  Row slices (spx.rt.gpu_rank/world, spx.rt.row_offset)
+ *  - A row slice reads and writes [row_lo, row_hi) of `rows` and `dr` and leaves the rest alone.
+ *  - It writes ALL of `cols` with this process' partial result; the caller all-reduces it: a sum for the two sum
+ *    kinds, a maximum for the max kind.
+ *  Results of spx_hip_mat_norms*
+ *  - kind SPX_HIP_NORM_SUM_ABS: rows[r] = sum_c |a(r,c)|, cols[c] = sum_r |a(r,c)| (their maxima are ||A||_inf and
+ *    ||A||_1); SPX_HIP_NORM_SUM_SQ: the sums of squares (the caller takes the root; their sum is ||A||_F^2);
+ *    SPX_HIP_NORM_MAX_ABS: the largest |a(r,c)|.  Only stored entries count, padding is never read into a result.
+ *  - A row or column with nothing stored gives +0.0.
+ *  - The sum kinds are accumulated atomically: within the fp64 bound of a sum of n non-negative terms in any order
+ *    (n * 2^-53 relative), not bit-reproducible.  The max kind is exact.
+ *  - Either of rows / cols may be NULL: it is not computed.
+ *  Scaling
+ *  - The new value of a stored a(r,c) is fl(fl(dr[r] * a) * dc[c]): two IEEE multiplications in this order.  With
+ *    dr or dc NULL that product is not formed at all.
+ *  - spx_hip_mat_scale rewrites the doubles in HBM.  Every later product sees the new values -- forward,
+ *    transposed, multi-vector, float, in parts -- and so do spx_hip_mat_get_diag*, spx_mat_get_entry /
+ *    spx_mat_set_entry and spx_mat_save.  The float copy (spx.gpu.values_f32) is rewritten in the same call, each
+ *    new double rounded to nearest even.
+ *  - Positions of the value array that hold no entry (pass padding, lanes beyond a piece's length) keep their bits.
+ *  - Diagonal and values plans stay valid; a later spx_hip_mat_set_values* simply overwrites with what the caller
+ *    hands over (a Newton code calls set_values, then scale, every outer iteration).
+ *  Encoded partitions
+ *  - They go stale exactly as after spx_hip_mat_set_values: spx_hip_mat_export_csx then fails and says so,
+ *    spx_hip_mat_export_units keeps working, spx_mat_save writes the file without them.  (A host-only matrix with a
+ *    values plan knows when a scaling has put back, bit for bit, the values held before the first update.)
+ *  Calling rules
+ *  - spx_hip_mat_norms and spx_hip_mat_scale only enqueue on `stream` (a hipStream_t): no allocation, no wait;
+ *    both are legal during stream capture, obey the handle's single-stream rule and count as "a product was
+ *    enqueued since the last edit" for spx_mat_set_entry's wait-once rule.
+ *  - The _host forms are synchronous: on a matrix in HBM through temporary device buffers, on a host-only matrix
+ *    (spx.rt.host_only) on the host threads over the host copy of the stream.
+ *  Failures: SPX_FAILURE through the error handler, nothing enqueued and nothing written, with a NULL handle, a
+ *  `kind` out of range, both outputs NULL, both scale vectors NULL, a calling thread whose current device is not
+ *  the matrix' one, a device form on a host-only matrix, a matrix tuned as a symmetric one (not served yet), and a
+ *  matrix with an exchange plan attached (spx_hip_mat_dist_attach). */
+#define SPX_HIP_NORM_SUM_ABS 0   /* rows: sum_c |a(r,c)|   cols: sum_r |a(r,c)|  */
+#define SPX_HIP_NORM_SUM_SQ  1   /* sums of squares (the caller takes the root)   */
+#define SPX_HIP_NORM_MAX_ABS 2
+spx_error_t spx_hip_mat_norms(const spx_matrix_t *A, int kind, spx_value_t *rows_dev, spx_value_t *cols_dev, void *stream);
+spx_error_t spx_hip_mat_norms_host(const spx_matrix_t *A, int kind, spx_value_t *rows, spx_value_t *cols);
+spx_error_t spx_hip_mat_scale(spx_matrix_t *A, const spx_value_t *dr_dev, const spx_value_t *dc_dev, void *stream);
+spx_error_t spx_hip_mat_scale_host(spx_matrix_t *A, const spx_value_t *dr, const spx_value_t *dc);
 
 /* The same for a caller compiled against another revision of this header: at most `size` bytes
  * (the caller's sizeof(spx_hip_info_t)) are written -- the struct only ever grows at its end.

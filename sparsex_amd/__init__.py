@@ -14,4 +14,5 @@ from .api import (  # noqa: F401
     SPX_DIST_REORDER_RCM, SPX_DIST_REORDER_RCM_OWNER,
     SPX_SUCCESS, SPX_FAILURE, SPX_INDEX_ZERO_BASED, SPX_INDEX_ONE_BASED,
     SPX_MAT_REORDER, SPX_VEC_AS_IS, SPX_VEC_TUNE,
+    NORM_SUM_ABS, NORM_SUM_SQ, NORM_MAX_ABS,
 )

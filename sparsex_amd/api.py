@@ -17,6 +17,10 @@ SPX_VEC_AS_IS = 43
 SPX_VEC_TUNE = 44
 SPX_INDEX_ZERO_BASED = 45
 SPX_INDEX_ONE_BASED = 46
+# kinds of Matrix.norms (SPX_HIP_NORM_* of include/sparsex_hip.h)
+NORM_SUM_ABS = 0
+NORM_SUM_SQ = 1
+NORM_MAX_ABS = 2
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -190,6 +194,11 @@ def lib():
     L.spx_hip_mat_diag_plan_get.argtypes = [vp, C.POINTER(DiagPlan)]
     L.spx_hip_vec_mul_elem.argtypes = [vp, vp, vp, vp]
     L.spx_hip_vec_reciprocal.argtypes = [vp, vp, d, vp]
+    L.spx_hip_vec_rsqrt.argtypes = [vp, vp, d, vp]
+    L.spx_hip_mat_norms.argtypes = [vp, i, vp, vp, vp]
+    L.spx_hip_mat_norms_host.argtypes = [vp, i, vp, vp]
+    L.spx_hip_mat_scale.argtypes = [vp, vp, vp, vp]
+    L.spx_hip_mat_scale_host.argtypes = [vp, vp, vp]
     L.spx_hip_vec_pcg_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.spx_hip_vec_pcg_direction.argtypes = [vp, vp, vp, vp, vp]
     L.spx_log_disable_all.restype = None
@@ -752,6 +761,127 @@ class Matrix:
             raise SpxError("spx_hip_mat_get_diag_host failed (see stderr)")
         return out
 
+    def _dev_operand(self, what, name, v, n, create):
+        """HBM address of the operand `name` of norms / scale: a DeviceVector or a 1-D contiguous float64 torch
+        tensor of `n` elements on the matrix' device; None stays None (0), True creates a DeviceVector where
+        `create`.  Returns (object, address, torch device or None)."""
+        if v is None:
+            return None, None, None
+        if v is True and create:
+            v = DeviceVector(n)
+        if isinstance(v, DeviceVector):
+            if v.size != n:
+                raise ValueError("%s: %s must have %d elements, not %d" % (what, name, n, v.size))
+            return v, v.data_ptr(), None
+        import torch
+        if not isinstance(v, torch.Tensor):
+            raise ValueError("%s: %s must be a DeviceVector or a torch tensor, not %s" % (what, name, type(v).__name__))
+        if v.dtype != torch.float64:
+            raise ValueError("%s: %s must be float64, not %s" % (what, name, v.dtype))
+        if v.dim() != 1 or v.shape[0] != n:
+            raise ValueError("%s: %s must have the shape (%d,), not %s" % (what, name, n, tuple(v.shape)))
+        if v.shape[0] > 1 and v.stride(0) != 1:
+            raise ValueError("%s: %s needs stride(0) == 1, not %d" % (what, name, v.stride(0)))
+        if v.device.type != "cuda":
+            raise ValueError("%s: %s must live on the matrix' HIP device, not on %s" % (what, name, v.device))
+        inf = self.info()
+        if inf.on_device and v.device.index != inf.device:
+            raise ValueError("%s: the matrix lives on cuda:%d, %s on %s" % (what, inf.device, name, v.device))
+        return v, v.data_ptr(), v.device
+
+    @staticmethod
+    def _raw_stream(stream, devices):
+        """a raw hipStream_t: of a torch stream, the number itself, or (None) the current torch stream where a
+        tensor takes part, else the null stream"""
+        if stream is not None:
+            return getattr(stream, "cuda_stream", stream)
+        devs = [dv for dv in devices if dv is not None]
+        if devs:
+            import torch
+            return torch.cuda.current_stream(devs[0]).cuda_stream
+        return 0
+
+    def hip_mat_norms(self, kind, rows_ptr, cols_ptr, stream=0):
+        """``spx_hip_mat_norms`` -- row norms to the nrows doubles in HBM at `rows_ptr`, column norms to the ncols
+        doubles at `cols_ptr` (either may be None), enqueue only."""
+        if lib().spx_hip_mat_norms(self.handle, kind, rows_ptr, cols_ptr, stream) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_norms failed (see stderr)")
+
+    def norms(self, kind, rows=None, cols=None, stream=None):
+        """Row and column norms of a general tune, in the numbering of the products' vectors: `kind` is NORM_SUM_ABS,
+        NORM_SUM_SQ (sums of squares) or NORM_MAX_ABS; `rows` (nrows elements) and `cols` (ncols) are DeviceVectors
+        or 1-D contiguous float64 torch tensors on the matrix' device, True (a new DeviceVector) or None (not
+        computed).  Enqueues on `stream` (a raw hipStream_t or a torch stream; default: the current torch stream
+        where a tensor takes part, else the null stream).  Returns (rows, cols)."""
+        if kind not in (NORM_SUM_ABS, NORM_SUM_SQ, NORM_MAX_ABS):
+            raise ValueError("norms: kind must be NORM_SUM_ABS, NORM_SUM_SQ or NORM_MAX_ABS, not %r" % (kind,))
+        if rows is None and cols is None:
+            raise ValueError("norms: rows and cols are both None")
+        rows, rp, rd = self._dev_operand("norms", "rows", rows, self.nrows, True)
+        cols, cp, cd = self._dev_operand("norms", "cols", cols, self.ncols, True)
+        self.hip_mat_norms(kind, rp, cp, self._raw_stream(stream, (rd, cd)))
+        return rows, cols
+
+    def norms_host(self, kind, rows=None, cols=None):
+        """``spx_hip_mat_norms_host`` -- (rows, cols) as numpy arrays of nrows and ncols doubles (synchronous; also
+        for host-only matrices).  `rows` / `cols`: None (a new array of zeros), a contiguous float64 array to write
+        into, or False (not computed, returned as None).  A row slice writes its own rows and leaves the others
+        alone, and writes its partial column result."""
+        if kind not in (NORM_SUM_ABS, NORM_SUM_SQ, NORM_MAX_ABS):
+            raise ValueError("norms_host: kind must be NORM_SUM_ABS, NORM_SUM_SQ or NORM_MAX_ABS, not %r" % (kind,))
+        out = []
+        for name, v, n in (("rows", rows, self.nrows), ("cols", cols, self.ncols)):
+            if v is None:
+                v = np.zeros(n)
+            elif v is False:
+                v = None
+            elif (not isinstance(v, np.ndarray) or v.dtype != np.float64 or v.ndim != 1 or v.size != n or
+                  not v.flags["C_CONTIGUOUS"]):
+                raise ValueError("norms_host: %s must be a contiguous float64 array of %d elements" % (name, n))
+            out.append(v)
+        if out[0] is None and out[1] is None:
+            raise ValueError("norms_host: rows and cols are both False")
+        # (an empty array has no address worth passing: a vector of no elements is never written)
+        keep = [None if v is None else (v if v.size else np.zeros(1)) for v in out]
+        ptr = [None if v is None else v.ctypes.data for v in keep]
+        if lib().spx_hip_mat_norms_host(self.handle, kind, ptr[0], ptr[1]) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_norms_host failed (see stderr)")
+        return out[0], out[1]
+
+    def hip_mat_scale(self, dr_ptr, dc_ptr, stream=0):
+        """``spx_hip_mat_scale`` -- A <- diag(dr) A diag(dc) in HBM from the nrows doubles at `dr_ptr` and the ncols
+        doubles at `dc_ptr` (either may be None), enqueue only."""
+        if lib().spx_hip_mat_scale(self.handle, dr_ptr, dc_ptr, stream) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_scale failed (see stderr)")
+
+    def scale(self, dr=None, dc=None, stream=None):
+        """A <- diag(dr) A diag(dc) in place, every stored value as fl(fl(dr[r] * a) * dc[c]); `dr` (nrows elements)
+        and `dc` (ncols), either may be None.  DeviceVectors or torch tensors on the matrix' device take the
+        device path (``spx_hip_mat_scale`` on `stream`, as in `norms`); numpy arrays the host path
+        (``spx_hip_mat_scale_host``, synchronous; also for host-only matrices)."""
+        if dr is None and dc is None:
+            raise ValueError("scale: dr and dc are both None")
+        given = [(name, v, n) for name, v, n in (("dr", dr, self.nrows), ("dc", dc, self.ncols)) if v is not None]
+        if any(isinstance(v, np.ndarray) for _, v, _ in given):
+            for name, v, n in given:
+                if not isinstance(v, np.ndarray):
+                    raise ValueError("scale: %s must be a numpy array like the other vector, not %s" % (name, type(v).__name__))
+                if v.dtype != np.float64:
+                    raise ValueError("scale: %s must be float64, not %s" % (name, v.dtype))
+                if v.ndim != 1 or v.shape[0] != n:
+                    raise ValueError("scale: %s must have the shape (%d,), not %s" % (name, n, tuple(v.shape)))
+                if not v.flags["C_CONTIGUOUS"]:
+                    raise ValueError("scale: %s must be contiguous" % name)
+            # (an empty array has no address worth passing: a vector of no elements is never read)
+            keep = [None if v is None else (v if v.size else np.zeros(1)) for v in (dr, dc)]
+            ptr = [None if v is None else v.ctypes.data for v in keep]
+            if lib().spx_hip_mat_scale_host(self.handle, ptr[0], ptr[1]) != SPX_SUCCESS:
+                raise SpxError("spx_hip_mat_scale_host failed (see stderr)")
+            return
+        _, rp, rd = self._dev_operand("scale", "dr", dr, self.nrows, False)
+        _, cp, cd = self._dev_operand("scale", "dc", dc, self.ncols, False)
+        self.hip_mat_scale(rp, cp, self._raw_stream(stream, (rd, cd)))
+
     def get_perm(self):
         """``spx_mat_get_perm`` -- perm[old index] = new index of a matrix tuned with
         ``reorder=True``; ``None`` when the matrix was not reordered."""
@@ -866,6 +996,20 @@ class DeviceVector:
 
     def reciprocal_into(self, dst, if_zero=0.0, stream=0):    # dst <- 1 / self, if_zero where self is +-0
         self._check(lib().spx_hip_vec_reciprocal(self.handle, dst.handle, if_zero, stream), "spx_hip_vec_reciprocal")
+
+    def rsqrt(self, dst=None, if_zero=0.0, stream=None):
+        """``spx_hip_vec_rsqrt`` -- dst <- 1 / sqrt(self), if_zero where self is +-0; `dst`: a DeviceVector of this
+        size (None: a new one; it may be this vector), `stream`: a raw hipStream_t or a torch stream (default the
+        null stream).  Returns dst."""
+        if dst is None:
+            dst = DeviceVector(self.size)
+        if not isinstance(dst, DeviceVector):
+            raise ValueError("rsqrt: dst must be a DeviceVector, not %s" % type(dst).__name__)
+        if dst.size != self.size:
+            raise ValueError("rsqrt: dst must have %d elements, not %d" % (self.size, dst.size))
+        st = 0 if stream is None else getattr(stream, "cuda_stream", stream)
+        self._check(lib().spx_hip_vec_rsqrt(self.handle, dst.handle, if_zero, st), "spx_hip_vec_rsqrt")
+        return dst
 
     def probe_read_write(self, dst, chunk_doubles, write_doubles, stream=0):
         """Diagnostic (spx_hip_probe_read_write): this vector read in chunks, `write_doubles` stored per chunk to dst."""

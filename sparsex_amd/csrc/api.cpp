@@ -16,6 +16,7 @@
 #include "encoder.hpp"
 #include "gpu_emit.hpp"
 #include "input.hpp"
+#include "mat_scale.hpp"
 #include "reorder.hpp"
 #include "stream_index.hpp"
 #include "threads.hpp"
@@ -2844,6 +2845,127 @@ try {
     return SPX_SUCCESS;
 } SPX_C_BOUNDARY(return SPX_FAILURE;)
 
+// ---- row / column norms and diagonal scaling of a tuned matrix -------------------------------------------
+// What a solver does to a matrix before it iterates -- look at its scaling and fix it (PETSc: MatGetRowMaxAbs,
+// MatGetColumnNorms, MatNorm, MatDiagonalScale) -- in one pass over the stream where it lies: scale_kernels.hip in
+// HBM, mat_scale.cpp on the host copy of a host-only matrix.  General tunes without an exchange plan.
+
+// the handle serves norms and scaling, or the message saying why not (`device_form`: the call takes HBM pointers)
+static bool scale_serves(const spx_matrix_t *A, const char *what, bool device_form)
+{
+    if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return false; }
+    if (A->symmetric) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, (std::string(what) + ": the matrix was tuned as a symmetric one -- norms and "
+                   "scaling serve general tunes only").c_str());
+        return false;
+    }
+    if (A->dist) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, (std::string(what) + ": no norms or scaling on a matrix with an exchange plan attached").c_str());
+        return false;
+    }
+    if (device_form && !A->dev) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, (std::string(what) + ": matrix was tuned with spx.rt.host_only=true: no HIP executor "
+                   "(the _host form works on the host copy)").c_str());
+        return false;
+    }
+    if (!device_form && !A->dev && !A->host_stream) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, "matrix holds no descriptor stream");
+        return false;
+    }
+    return true;
+}
+
+spx_error_t spx_hip_mat_norms(const spx_matrix_t *A_, int kind, spx_value_t *rows_dev, spx_value_t *cols_dev, void *stream)
+try {
+    spx_matrix_t *A = const_cast<spx_matrix_t *>(A_);
+    if (!scale_serves(A, "spx_hip_mat_norms", true)) return SPX_FAILURE;
+    if (kind < SPX_HIP_NORM_SUM_ABS || kind > SPX_HIP_NORM_MAX_ABS) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_norms: kind is none of SPX_HIP_NORM_SUM_ABS, _SUM_SQ, _MAX_ABS");
+        return SPX_FAILURE;
+    }
+    if (!rows_dev && !cols_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_norms: rows and cols are both NULL"); return SPX_FAILURE; }
+    try {
+        device_mat_norms(A->dev, kind, rows_dev, cols_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_norms_host(const spx_matrix_t *A_, int kind, spx_value_t *rows, spx_value_t *cols)
+try {
+    spx_matrix_t *A = const_cast<spx_matrix_t *>(A_);
+    if (!scale_serves(A, "spx_hip_mat_norms_host", false)) return SPX_FAILURE;
+    if (kind < SPX_HIP_NORM_SUM_ABS || kind > SPX_HIP_NORM_MAX_ABS) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_norms_host: kind is none of SPX_HIP_NORM_SUM_ABS, _SUM_SQ, _MAX_ABS");
+        return SPX_FAILURE;
+    }
+    if (!rows && !cols) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_norms_host: rows and cols are both NULL"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    try {
+        if (A->host_stream)
+            host_mat_norms(*A->host_stream, kind, (size_t) A->nrows, (size_t) A->ncols, (size_t) A->own_lo,
+                           (size_t) A->own_hi, rows, cols, host_threads());
+        else
+            device_mat_norms_host(A->dev, kind, rows, cols);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_scale(spx_matrix_t *A, const spx_value_t *dr_dev, const spx_value_t *dc_dev, void *stream)
+try {
+    if (!scale_serves(A, "spx_hip_mat_scale", true)) return SPX_FAILURE;
+    if (!dr_dev && !dc_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_scale: dr and dc are both NULL"); return SPX_FAILURE; }
+    try {
+        device_mat_scale(A->dev, dr_dev, dc_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    // (the encoded partitions go stale as after spx_hip_mat_set_values)
+    if (!A->values_refreshed) {
+        std::lock_guard<std::mutex> lk(A->mtx);
+        values_were_refreshed(A);
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_scale_host(spx_matrix_t *A, const spx_value_t *dr, const spx_value_t *dc)
+try {
+    if (!scale_serves(A, "spx_hip_mat_scale_host", false)) return SPX_FAILURE;
+    if (!dr && !dc) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_scale_host: dr and dc are both NULL"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    bool as_before = false;
+    try {
+        if (A->host_stream) {
+            // (the rule of spx_hip_mat_set_values_host: with a values plan at hand, remember what the first bulk
+            // update replaces and notice when one has put it back; without one the partitions stay stale)
+            const bool digests = A->values_plan != nullptr;
+            if (digests && !A->values_refreshed && !A->parts.empty()) {
+                A->pre_refresh_digest = values_plan_digest(*A->values_plan, *A->host_stream, host_threads());
+                A->has_pre_refresh_digest = true;
+                A->edited_while_stale = false;
+            }
+            host_mat_scale(*A->host_stream, (size_t) A->nrows, (size_t) A->ncols, dr, dc, host_threads());
+            if (!digests) A->edited_while_stale = true;
+            as_before = digests && A->has_pre_refresh_digest && !A->edited_while_stale &&
+                        values_plan_digest(*A->values_plan, *A->host_stream, host_threads()) == A->pre_refresh_digest;
+        } else {
+            device_mat_scale_host(A->dev, dr, dc);
+        }
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    if (as_before) A->values_refreshed = false;
+    else values_were_refreshed(A);
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
 spx_error_t spx_hip_mat_info_sized(const spx_matrix_t *A, void *info, size_t size)
 try {
     spx_hip_info_t full;
@@ -2925,7 +3047,7 @@ try {
     std::lock_guard<std::mutex> lk(A->mtx);
     if (A->values_refreshed) {
         SETERROR_1(SPX_ERR_TUNED_MAT, "the values of the encoded partitions are stale: the matrix took new values "
-                   "through spx_hip_mat_set_values (spx_hip_mat_export_units still shows the pattern)");
+                   "through spx_hip_mat_set_values or spx_hip_mat_scale (spx_hip_mat_export_units still shows the pattern)");
         return SPX_FAILURE;
     }
     size_t li = (size_t) part - A->first_part;

@@ -201,6 +201,19 @@ size_t device_diag_plan_set(DeviceMatrix *m, const DiagPlan &plan);
 void device_diag_plan_drop(DeviceMatrix *m);
 void device_get_diag(DeviceMatrix *m, double *d_diag, void *stream);
 void device_get_diag_host(DeviceMatrix *m, double *h_diag);
+// Row and column norms and diagonal scaling of a GENERAL stream where it lies (scale_kernels.hip; the caller keeps
+// symmetric and attached matrices away).  `kind`: NORM_SUM_ABS / NORM_SUM_SQ / NORM_MAX_ABS (spmv_launch.hpp).
+// device_mat_norms zero-fills d_rows[own_lo, own_hi) and all ncols of d_cols, then one csx_norms_kernel launch per
+// launch of the forward product adds to them; either pointer may be null.  device_mat_scale rewrites the doubles
+// in HBM, a(r,c) <- fl(fl(dr[r] * a) * dc[c]) (either vector may be null: that product is not formed), and the float
+// twin in the same launches.  Both only enqueue on `stream` -- no allocation, no wait, legal during stream capture
+// -- refuse a calling thread whose current device is not the matrix' one, and count as a product for
+// device_poke's wait-once rule.  The _host forms: the same through temporary HBM buffers, synchronous (a row slice
+// reads and writes [own_lo, own_hi) of h_rows / h_dr).
+void device_mat_norms(DeviceMatrix *m, int kind, double *d_rows, double *d_cols, void *stream);
+void device_mat_scale(DeviceMatrix *m, const double *d_dr, const double *d_dc, void *stream);
+void device_mat_norms_host(DeviceMatrix *m, int kind, double *h_rows, double *h_cols);
+void device_mat_scale_host(DeviceMatrix *m, const double *h_dr, const double *h_dc);
 size_t device_n_values(const DeviceMatrix *m);     // doubles in the stream's value array
 
 struct DeviceMatrixInfo {

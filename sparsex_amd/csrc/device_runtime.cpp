@@ -2,7 +2,7 @@
 // (DeviceMatrix, device_upload), the choice of kernel for a product and its launches, the product in parts,
 // the host-vector entry point with its staging copies, page-locking, download, peek / poke and info.
 // Plain C++ on the HIP runtime API; the kernels and their launchers are in spmv_kernels.hip,
-// spmv_xw_kernels.hip, spmv_sx_kernels.hip and spmv_t_kernels.hip (spmv_launch.hpp).
+// spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_t_kernels.hip and scale_kernels.hip (spmv_launch.hpp).
 #include "device.hpp"
 #include "hip_check.hpp"
 #include "spmv_launch.hpp"
@@ -1963,6 +1963,121 @@ void device_get_diag_host(DeviceMatrix *m, double *h_diag)
         quiesce_before_edit(m);
         enqueue_own_diag(m, d, st);
         HIP_CHECK(hipMemcpyAsync(h_diag + m->own_lo, d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        m->launched_since_edit = false;
+    } catch (...) {
+        (void) hipStreamSynchronize(st);
+        (void) hipFree(d);
+        throw;
+    }
+    (void) hipFree(d);
+}
+
+// ---- norms and diagonal scaling of a general stream (scale_kernels.hip) --------------------------------------
+// One launch per launch of the forward product (column phases, slices in one launch and plain streams alike) over
+// the plain pass headers and descriptors, as device_spmv_trans walks them.
+static void need_own_device(const DeviceMatrix *m)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != m->device)
+        throw FatalError("the matrix lives on HIP device " + std::to_string(m->device) +
+                         ", the calling thread's current device is " + std::to_string(cur));
+}
+
+static void need_general_stream(const DeviceMatrix *m, const char *what)
+{
+    if (m->symmetric || m->has_tiles)
+        throw FatalError(std::string(what) + ": the matrix was tuned as a symmetric one (general tunes only)");
+}
+
+void device_mat_norms(DeviceMatrix *m, int kind, double *d_rows, double *d_cols, void *stream_)
+{
+    need_general_stream(m, "norms");
+    need_own_device(m);
+    if (kind != NORM_SUM_ABS && kind != NORM_SUM_SQ && kind != NORM_MAX_ABS) throw FatalError("norms: no such kind");
+    if (!d_rows && !d_cols) return;
+    m->launched_since_edit = true;
+    if (d_rows && m->own_hi > m->own_lo) launch_scale(stream_, 1, d_rows, 0, m->own_lo, m->own_hi, 0.0);
+    if (d_cols && m->ncols) launch_scale(stream_, 1, d_cols, 0, 0, m->ncols, 0.0);
+    NormArgs a{};
+    a.rbs = m->rbs; a.values = m->values; a.cidx = m->cidx; a.segrows = m->segrows;
+    a.passes = m->passes; a.descs = m->descs;
+    a.rows = d_rows; a.cols = d_cols; a.pass_stride = m->pass_stride;
+    const size_t lds = (((size_t) m->mv_rows + 1u) & ~(size_t) 1) * sizeof(double);
+    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
+        const uint32_t blocks = 8u * m->xcd_longest[ph];
+        if (blocks) launch_norms(kind, m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+void device_mat_scale(DeviceMatrix *m, const double *d_dr, const double *d_dc, void *stream_)
+{
+    need_general_stream(m, "scale");
+    need_own_device(m);
+    if (!d_dr && !d_dc) return;
+    m->launched_since_edit = true;
+    ScaleArgs a{};
+    a.rbs = m->rbs; a.values = m->values; a.cidx = m->cidx; a.segrows = m->segrows;
+    a.passes = m->passes; a.descs = m->descs;
+    a.dr = d_dr; a.dc = d_dc; a.values_rw = m->values; a.values_f32 = m->values_f32; a.pass_stride = m->pass_stride;
+    const size_t lds = (((size_t) m->mv_rows + 1u) & ~(size_t) 1) * sizeof(double);
+    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
+        const uint32_t blocks = 8u * m->xcd_longest[ph];
+        if (blocks) launch_scale_values(m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+// (the host forms: temporary buffers of nrows + ncols doubles, the matrix' own stream, a wait)
+void device_mat_norms_host(DeviceMatrix *m, int kind, double *h_rows, double *h_cols)
+{
+    need_general_stream(m, "norms");
+    need_own_device(m);
+    if (!h_rows && !h_cols) return;
+    if (!m->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking));
+    hipStream_t st = m->host_stream;
+    const size_t n_own = m->own_hi - m->own_lo;
+    double *d = nullptr;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), (m->nrows + m->ncols + 1) * sizeof(double)));
+    try {
+        // (values a client's streams are still writing are not ordered against this stream: wait for them as
+        // device_poke does, once)
+        quiesce_before_edit(m);
+        device_mat_norms(m, kind, h_rows ? d : nullptr, h_cols ? d + m->nrows : nullptr, st);
+        if (h_rows && n_own)
+            HIP_CHECK(hipMemcpyAsync(h_rows + m->own_lo, d + m->own_lo, n_own * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (h_cols && m->ncols)
+            HIP_CHECK(hipMemcpyAsync(h_cols, d + m->nrows, m->ncols * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        m->launched_since_edit = false;
+    } catch (...) {
+        (void) hipStreamSynchronize(st);
+        (void) hipFree(d);
+        throw;
+    }
+    (void) hipFree(d);
+}
+
+void device_mat_scale_host(DeviceMatrix *m, const double *h_dr, const double *h_dc)
+{
+    need_general_stream(m, "scale");
+    need_own_device(m);
+    if (!h_dr && !h_dc) return;
+    if (!m->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking));
+    hipStream_t st = m->host_stream;
+    const size_t n_own = m->own_hi - m->own_lo;
+    double *d = nullptr;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), (m->nrows + m->ncols + 1) * sizeof(double)));
+    try {
+        if (h_dr && n_own)
+            HIP_CHECK(hipMemcpyAsync(d + m->own_lo, h_dr + m->own_lo, n_own * sizeof(double), hipMemcpyHostToDevice, st));
+        if (h_dc && m->ncols)
+            HIP_CHECK(hipMemcpyAsync(d + m->nrows, h_dc, m->ncols * sizeof(double), hipMemcpyHostToDevice, st));
+        // (products a client enqueued on streams of its own are not ordered against this one: wait for them as
+        // device_poke does, once)
+        quiesce_before_edit(m);
+        device_mat_scale(m, h_dr ? d : nullptr, h_dc ? d + m->nrows : nullptr, st);
         HIP_CHECK(hipStreamSynchronize(st));
         m->launched_since_edit = false;
     } catch (...) {

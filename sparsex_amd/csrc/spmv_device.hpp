@@ -123,6 +123,24 @@ __device__ __forceinline__ PassValues<W, V> load_values(const StreamArgs &a, con
     return v;
 }
 
+// the value store (csx_scale_values_kernel): what load_values read, back to where it lay -- 16 bytes per lane and
+// pair (floats: 8).  `values`: the array of doubles, or its float twin.  `len` (a piece of a gather pass): the
+// positions len .. W - 1 of the lane are padding and keep their bits
+template <int W, class V = double>
+__device__ __forceinline__ void store_values(V *values, const SpxRowBlock &rb, const SpxPass &ps, uint32_t l,
+                                             const PassValues<W, V> &v, int len = W)
+{
+    const uint32_t nseg = ps.nseg;
+    V *vals = values + rb.val_off + ps.val_off;
+#pragma unroll
+    for (int p = 0; p < W / 2; ++p) {
+        V *dst = vals + (uint32_t) p * 2u * nseg + l * 2u;
+        if (2 * p + 1 < len) *reinterpret_cast<typename ValueVec<V>::pair *>(dst) = v.v2[p];
+        else if (2 * p < len) dst[0] = v.v2[p].x;
+    }
+    if ((W & 1) && W - 1 < len) vals[(uint32_t) (W / 2) * 2u * nseg + l] = v.v1;
+}
+
 // the values of a pass as doubles (V = double: as they are): the members load_values wrote, W / 2 pairs and the
 // odd last one
 template <int W, class V>

@@ -1,8 +1,9 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the nine interpreter translation
+// XCD-aware row-block order, the kernel families and the launchers of the ten interpreter translation
 // units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_t_kernels.hip, spmv_mv_kernels.hip,
-// spmv_mv_f32_kernels.hip, spmv_mvr_kernels.hip, spmv_mvr_f32_kernels.hip, spmv_mvsym_kernels.hip).  Plain C++: no
-// HIP header, so that the host runtime (device_runtime.cpp) is compiled by the host compiler.
+// spmv_mv_f32_kernels.hip, spmv_mvr_kernels.hip, spmv_mvr_f32_kernels.hip, spmv_mvsym_kernels.hip,
+// scale_kernels.hip).  Plain C++: no HIP header, so that the host runtime (device_runtime.cpp) is compiled by the
+// host compiler.
 #pragma once
 
 #include "gpu_format.h"
@@ -114,6 +115,28 @@ struct TransArgs : StreamArgs {
 void launch_spmv_t(bool windows, int waves, unsigned blocks, size_t lds_bytes, void *stream, const TransArgs &a,
                    const XcdSplit &xs);
 void spmv_t_allow_lds(size_t bytes);
+
+// scale_kernels.hip: one pass over a general stream where it lies, as csx_spmv_t_kernel walks it (the PLAIN pass
+// headers and descriptors, one launch per entry of the matrix' XCD splits).
+// csx_scale_values_kernel: a(r,c) <- fl(fl(dr[r] * a) * dc[c]) in place (a null vector: its product is not formed),
+// and the float twin of the values, where there is one, rewritten by the same lane.  lds_bytes: the most rows of a
+// row-block (dr of its rows).
+struct ScaleArgs : StreamArgs {
+    const double *dr, *dc;   // nrows / ncols doubles, either may be null
+    double *values_rw;       // StreamArgs::values, to be written
+    float *values_f32;       // its float twin, or null
+    uint32_t pass_stride;
+};
+void launch_scale_values(int waves, unsigned blocks, size_t lds_bytes, void *stream, const ScaleArgs &a, const XcdSplit &xs);
+// csx_norms_kernel<KIND>: rows[r] (+)= |a(r,c)|, a(r,c)^2 or max |a(r,c)| over the stored entries of row r, cols[c]
+// the same over column c; both through atomics, on top of a pass that zero-filled them; either may be null.
+// lds_bytes: the most rows of a row-block (its rows' results), also where rows is null.
+constexpr int NORM_SUM_ABS = 0, NORM_SUM_SQ = 1, NORM_MAX_ABS = 2;
+struct NormArgs : StreamArgs {
+    double *rows, *cols;
+    uint32_t pass_stride;
+};
+void launch_norms(int kind, int waves, unsigned blocks, size_t lds_bytes, void *stream, const NormArgs &a, const XcdSplit &xs);
 
 // spmv_mv_kernels.hip: the multi-vector product, K = 2, 4 or 8 vectors per pass over the plain stream.
 // Column-major blocks: vector j of X at x + j * ldx, of Y at y + j * ldy.

@@ -82,9 +82,11 @@ __device__ __forceinline__ double mul_rn(double a, double b)
 
 // 1 / a, or s where a is +-0: one IEEE division
 __device__ __forceinline__ double recip_or(double a, double s) { return a == 0.0 ? s : 1.0 / a; }
+// 1 / sqrt(a), or s where a is +-0: one IEEE square root, one IEEE division
+__device__ __forceinline__ double rsqrt_or(double a, double s) { return a == 0.0 ? s : 1.0 / sqrt(a); }
 
 // kind: 0 init (d = s), 1 scale (d = s*a), 2 axpy (d = a + s*b), 3 copy (d = a), 4 product (d = a .* b),
-// 5 reciprocal (d = 1 / a, s where a is +-0)
+// 5 reciprocal (d = 1 / a, s where a is +-0), 6 reciprocal square root (d = 1 / sqrt(a), s where a is +-0)
 template <int KIND>
 __device__ __forceinline__ double2 vec_map_one(double2 va, double2 vb, double s)
 {
@@ -93,6 +95,7 @@ __device__ __forceinline__ double2 vec_map_one(double2 va, double2 vb, double s)
     if (KIND == 3) return va;
     if (KIND == 4) return make_double2(mul_rn(va.x, vb.x), mul_rn(va.y, vb.y));
     if (KIND == 5) return make_double2(recip_or(va.x, s), recip_or(va.y, s));
+    if (KIND == 6) return make_double2(rsqrt_or(va.x, s), rsqrt_or(va.y, s));
     return make_double2(va.x + s * vb.x, va.y + s * vb.y);
 }
 
@@ -104,7 +107,7 @@ __device__ __forceinline__ void vec_map_chunk(double *__restrict__ d, const doub
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         const size_t i = n - 1;
         d[i] = KIND == 0 ? s : KIND == 1 ? s * a[i] : KIND == 3 ? a[i] : KIND == 4 ? mul_rn(a[i], b[i]) :
-               KIND == 5 ? recip_or(a[i], s) : a[i] + s * b[i];
+               KIND == 5 ? recip_or(a[i], s) : KIND == 6 ? rsqrt_or(a[i], s) : a[i] + s * b[i];
     }
     size_t lo, hi;
     if (!vec_chunk(n / 2, nchunks, per, chunk_len, lo, hi)) return;
@@ -671,6 +674,12 @@ spx_error_t spx_hip_vec_reciprocal(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, s
 {
     if (same_size(v1, v2) != SPX_SUCCESS) return SPX_FAILURE;
     return map<5>(v2, v1, nullptr, if_zero, stream);
+}
+
+spx_error_t spx_hip_vec_rsqrt(const spx_hip_vec_t *v1, spx_hip_vec_t *v2, spx_value_t if_zero, void *stream)
+{
+    if (same_size(v1, v2) != SPX_SUCCESS) return SPX_FAILURE;
+    return map<6>(v2, v1, nullptr, if_zero, stream);
 }
 
 spx_error_t spx_hip_vec_pcg_update(spx_hip_vec_t *x, const spx_hip_vec_t *p, spx_hip_vec_t *r, const spx_hip_vec_t *ap,
