@@ -16,7 +16,7 @@ HOST_SRCS := common.cpp config.cpp partition.cpp stats.cpp encoder.cpp input.cpp
              csx_emit.cpp gpu_emit.cpp stream_index.cpp xwindows.cpp sxplan.cpp values_plan.cpp diag_plan.cpp mat_scale.cpp dist.cpp api.cpp \
              device_runtime.cpp dist_rccl.cpp
 HOST_OBJS := $(HOST_SRCS:%.cpp=$(OBJDIR)/%.o)
-HIP_OBJ   := $(OBJDIR)/spmv_kernels.o $(OBJDIR)/spmv_xw_kernels.o $(OBJDIR)/spmv_sx_kernels.o $(OBJDIR)/spmv_t_kernels.o $(OBJDIR)/scale_kernels.o $(OBJDIR)/spmv_mv_kernels.o $(OBJDIR)/spmv_mv_f32_kernels.o $(OBJDIR)/spmv_mvr_kernels.o $(OBJDIR)/spmv_mvr_f32_kernels.o $(OBJDIR)/spmv_mvsym_kernels.o $(OBJDIR)/vec_kernels.o $(OBJDIR)/dist_kernels.o $(OBJDIR)/refresh_kernels.o
+HIP_OBJ   := $(OBJDIR)/spmv_kernels.o $(OBJDIR)/spmv_xw_kernels.o $(OBJDIR)/spmv_sx_kernels.o $(OBJDIR)/spmv_t_kernels.o $(OBJDIR)/scale_kernels.o $(OBJDIR)/sym_scale_kernels.o $(OBJDIR)/spmv_mv_kernels.o $(OBJDIR)/spmv_mv_f32_kernels.o $(OBJDIR)/spmv_mvr_kernels.o $(OBJDIR)/spmv_mvr_f32_kernels.o $(OBJDIR)/spmv_mvsym_kernels.o $(OBJDIR)/vec_kernels.o $(OBJDIR)/dist_kernels.o $(OBJDIR)/refresh_kernels.o
 
 # (the host sources that drive the GPU -- device_runtime.cpp, dist_rccl.cpp -- use the HIP runtime API only)
 CXXFLAGS  := -std=c++17 -O2 -g -fPIC -Wall -Iinclude -I$(CSRC) -pthread -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include

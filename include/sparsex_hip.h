@@ -853,8 +853,8 @@ spx_error_t spx_hip_mat_diag_plan_get(const spx_matrix_t *A, spx_hip_diag_plan_t
  *    (spx.rt.host_only) on the host threads over the host copy of the stream.
  *  Failures: SPX_FAILURE through the error handler, nothing enqueued and nothing written, with a NULL handle, a
  *  `kind` out of range, both outputs NULL, both scale vectors NULL, a calling thread whose current device is not
- *  the matrix' one, a device form on a host-only matrix, a matrix tuned as a symmetric one (not served yet), and a
- *  matrix with an exchange plan attached (spx_hip_mat_dist_attach). */
+ *  the matrix' one, a device form on a host-only matrix, a matrix tuned as a symmetric one (served by spx_hip_mat_sym_norms
+ *  / spx_hip_mat_sym_scale below), and a matrix with an exchange plan attached (spx_hip_mat_dist_attach). */
 #define SPX_HIP_NORM_SUM_ABS 0   /* rows: sum_c |a(r,c)|   cols: sum_r |a(r,c)|  */
 #define SPX_HIP_NORM_SUM_SQ  1   /* sums of squares (the caller takes the root)   */
 #define SPX_HIP_NORM_MAX_ABS 2
@@ -862,6 +862,56 @@ spx_error_t spx_hip_mat_norms(const spx_matrix_t *A, int kind, spx_value_t *rows
 spx_error_t spx_hip_mat_norms_host(const spx_matrix_t *A, int kind, spx_value_t *rows, spx_value_t *cols);
 spx_error_t spx_hip_mat_scale(spx_matrix_t *A, const spx_value_t *dr_dev, const spx_value_t *dc_dev, void *stream);
 spx_error_t spx_hip_mat_scale_host(spx_matrix_t *A, const spx_value_t *dr, const spx_value_t *dc);
+
+/* Norms and the scaling D * A * D of a matrix tuned as a symmetric one, where it lies: the read-once tiles and
+ * segments, the lower copies and mirror images, the diagonal array and the thin mirror list of a row slice, whatever
+ * kernel family the product runs (whole matrices, row slices, reordered matrices, spx.gpu.deterministic, with or
+ * without the float copy spx.gpu.values_f32=all).  A symmetric matrix has ONE norm vector -- the norm of row i is
+ * that of column i -- and only the scaling with the same vector on both sides keeps it symmetric.
+ *
+ *  Vectors
+ *  - `out` and `d` hold nrows doubles in the numbering of the products' vectors (the tuned one under
+ *    SPX_MAT_REORDER / spx.rt.dist_reorder), 8-byte aligned; the _dev pointers lie in HBM of the matrix' device.
+ *  Norms
+ *  - out[i] is the norm of row i of the full matrix, which is also that of column i; `kind` as above.
+ *  - Only stored entries count.  An off-diagonal entry that the stream holds once (read-once tile or segment)
+ *    counts for its row and for its column; an entry that it holds twice (lower copy and mirror image) counts once
+ *    per copy, for that copy's row; the diagonal counts for its row.  A row with nothing stored gives +0.0.
+ *  - The max kind is exact.  The sum kinds are accumulated atomically: within n * 2^-53 relative, not
+ *    bit-reproducible.
+ *  Scaling
+ *  - The new value of a stored a(r,c) is fl(fl(d[max(r,c)] * a) * d[min(r,c)]): two IEEE multiplications, the
+ *    factor of the larger index first.  For the stored lower triangle that is spx_hip_mat_scale(A, d, d)'s
+ *    fl(fl(d[r] * a) * d[c]); a mirror image gets the bits of its lower copy, so the stored matrix stays symmetric
+ *    bit for bit.  The diagonal becomes fl(fl(d[i] * a) * d[i]).
+ *  - The float copy (spx.gpu.values_f32=all) is rewritten in the same call, each new double rounded to nearest
+ *    even; the diagonal array and the thin mirror list have no float twin and stay doubles.
+ *  - Scaling by powers of two is exact and undone by their reciprocals.
+ *  - Not written: pass padding, lanes beyond a gather piece, a position of a row-block pass with row == column
+ *    (the zero a block holds where it closes over the diagonal; it is not counted either), and a +-0 inside a pass
+ *    of 8x8 tiles (a cell the matrix need not hold): they keep their bits.
+ *  Row slices (spx.rt.gpu_rank/world, spx.rt.row_offset, no exchange plan)
+ *  - The process accounts for the lower triangle and the diagonal of its own rows; the mirror image of those
+ *    entries lands on rows in front of the slice.  spx_hip_mat_sym_norms* therefore writes ALL nrows elements of
+ *    `out` with this process' partial result, zero where it holds nothing, and the caller all-reduces: a sum for
+ *    the two sum kinds, a maximum for the max kind.
+ *  - spx_hip_mat_sym_scale* reads `d` wherever its entries reach, that is over all of [0, row_hi).  Every process
+ *    scales with the same `d`.
+ *  Everything else as for spx_hip_mat_norms / spx_hip_mat_scale
+ *  - The device forms only enqueue on `stream`: no allocation, no wait, legal during stream capture; the
+ *    single-stream rule holds and they count as "a product was enqueued since the last edit".
+ *  - The _host forms are synchronous; on a host-only matrix they work on the host copy of the stream.
+ *  - Later products, spx_hip_mat_get_diag*, spx_mat_get_entry and spx_mat_save see the scaled matrix; values and
+ *    diagonal plans stay valid; the encoded partitions go stale exactly as after spx_hip_mat_set_values, with the
+ *    same digest rule on a host-only matrix with a values plan.
+ *  Failures: SPX_FAILURE through the error handler, nothing enqueued and nothing written, with a NULL handle, a
+ *  matrix tuned as a general one (spx_hip_mat_norms / spx_hip_mat_scale(A, d, d) serve it), a matrix with an exchange
+ *  plan attached, a device form on a host-only matrix, a calling thread whose current device is not the matrix'
+ *  one, a `kind` out of range and a NULL vector. */
+spx_error_t spx_hip_mat_sym_norms(const spx_matrix_t *A, int kind, spx_value_t *out_dev, void *stream);
+spx_error_t spx_hip_mat_sym_norms_host(const spx_matrix_t *A, int kind, spx_value_t *out);
+spx_error_t spx_hip_mat_sym_scale(spx_matrix_t *A, const spx_value_t *d_dev, void *stream);
+spx_error_t spx_hip_mat_sym_scale_host(spx_matrix_t *A, const spx_value_t *d);
 
 /* The same for a caller compiled against another revision of this header: at most `size` bytes
  * (the caller's sizeof(spx_hip_info_t)) are written -- the struct only ever grows at its end.

@@ -199,6 +199,10 @@ def lib():
     L.spx_hip_mat_norms_host.argtypes = [vp, i, vp, vp]
     L.spx_hip_mat_scale.argtypes = [vp, vp, vp, vp]
     L.spx_hip_mat_scale_host.argtypes = [vp, vp, vp]
+    L.spx_hip_mat_sym_norms.argtypes = [vp, i, vp, vp]
+    L.spx_hip_mat_sym_norms_host.argtypes = [vp, i, vp]
+    L.spx_hip_mat_sym_scale.argtypes = [vp, vp, vp]
+    L.spx_hip_mat_sym_scale_host.argtypes = [vp, vp]
     L.spx_hip_vec_pcg_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.spx_hip_vec_pcg_direction.argtypes = [vp, vp, vp, vp, vp]
     L.spx_log_disable_all.restype = None
@@ -881,6 +885,67 @@ class Matrix:
         _, rp, rd = self._dev_operand("scale", "dr", dr, self.nrows, False)
         _, cp, cd = self._dev_operand("scale", "dc", dc, self.ncols, False)
         self.hip_mat_scale(rp, cp, self._raw_stream(stream, (rd, cd)))
+
+    def hip_mat_sym_norms(self, kind, out_ptr, stream=0):
+        """``spx_hip_mat_sym_norms`` -- the norms of a symmetric tune's rows (= columns) to the nrows doubles in HBM at
+        `out_ptr`, enqueue only."""
+        if lib().spx_hip_mat_sym_norms(self.handle, kind, out_ptr, stream) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_sym_norms failed (see stderr)")
+
+    def sym_norms(self, kind, out=None, stream=None):
+        """Norms of a symmetric tune, in the numbering of the products' vectors: out[i] is the norm of row i of the
+        full matrix, which is that of column i.  `kind` as in `norms`; `out` (nrows elements) is a DeviceVector or a
+        1-D contiguous float64 torch tensor on the matrix' device, or None (a new DeviceVector).  A row slice writes
+        ALL of `out` with its partial result; the caller all-reduces.  Enqueues on `stream` as `norms` does.
+        Returns `out`."""
+        if kind not in (NORM_SUM_ABS, NORM_SUM_SQ, NORM_MAX_ABS):
+            raise ValueError("sym_norms: kind must be NORM_SUM_ABS, NORM_SUM_SQ or NORM_MAX_ABS, not %r" % (kind,))
+        out, op, od = self._dev_operand("sym_norms", "out", True if out is None else out, self.nrows, True)
+        self.hip_mat_sym_norms(kind, op, self._raw_stream(stream, (od,)))
+        return out
+
+    def sym_norms_host(self, kind, out=None):
+        """``spx_hip_mat_sym_norms_host`` -- the same as a numpy array of nrows doubles (synchronous; also for
+        host-only matrices).  `out`: None (a new array) or a contiguous float64 array to write into."""
+        if kind not in (NORM_SUM_ABS, NORM_SUM_SQ, NORM_MAX_ABS):
+            raise ValueError("sym_norms_host: kind must be NORM_SUM_ABS, NORM_SUM_SQ or NORM_MAX_ABS, not %r" % (kind,))
+        if out is None:
+            out = np.zeros(self.nrows)
+        elif (not isinstance(out, np.ndarray) or out.dtype != np.float64 or out.ndim != 1 or out.size != self.nrows or
+              not out.flags["C_CONTIGUOUS"]):
+            raise ValueError("sym_norms_host: out must be a contiguous float64 array of %d elements" % self.nrows)
+        keep = out if out.size else np.zeros(1)
+        if lib().spx_hip_mat_sym_norms_host(self.handle, kind, keep.ctypes.data) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_sym_norms_host failed (see stderr)")
+        return out
+
+    def hip_mat_sym_scale(self, d_ptr, stream=0):
+        """``spx_hip_mat_sym_scale`` -- A <- diag(d) A diag(d) of a symmetric tune in HBM from the nrows doubles at
+        `d_ptr`, enqueue only."""
+        if lib().spx_hip_mat_sym_scale(self.handle, d_ptr, stream) != SPX_SUCCESS:
+            raise SpxError("spx_hip_mat_sym_scale failed (see stderr)")
+
+    def sym_scale(self, d, stream=None):
+        """A <- diag(d) A diag(d) of a symmetric tune in place, every stored value as
+        fl(fl(d[max(r,c)] * a) * d[min(r,c)]), so that the stored matrix stays symmetric bit for bit; `d` has nrows
+        elements.  A DeviceVector or a torch tensor on the matrix' device takes the device path
+        (``spx_hip_mat_sym_scale`` on `stream`, as in `norms`); a numpy array the host path
+        (``spx_hip_mat_sym_scale_host``, synchronous; also for host-only matrices)."""
+        if d is None:
+            raise ValueError("sym_scale: d is None")
+        if isinstance(d, np.ndarray):
+            if d.dtype != np.float64:
+                raise ValueError("sym_scale: d must be float64, not %s" % d.dtype)
+            if d.ndim != 1 or d.shape[0] != self.nrows:
+                raise ValueError("sym_scale: d must have the shape (%d,), not %s" % (self.nrows, tuple(d.shape)))
+            if not d.flags["C_CONTIGUOUS"]:
+                raise ValueError("sym_scale: d must be contiguous")
+            keep = d if d.size else np.zeros(1)
+            if lib().spx_hip_mat_sym_scale_host(self.handle, keep.ctypes.data) != SPX_SUCCESS:
+                raise SpxError("spx_hip_mat_sym_scale_host failed (see stderr)")
+            return
+        _, dp, dd = self._dev_operand("sym_scale", "d", d, self.nrows, False)
+        self.hip_mat_sym_scale(dp, self._raw_stream(stream, (dd,)))
 
     def get_perm(self):
         """``spx_mat_get_perm`` -- perm[old index] = new index of a matrix tuned with

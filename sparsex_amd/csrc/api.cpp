@@ -2850,13 +2850,19 @@ try {
 // MatGetColumnNorms, MatNorm, MatDiagonalScale) -- in one pass over the stream where it lies: scale_kernels.hip in
 // HBM, mat_scale.cpp on the host copy of a host-only matrix.  General tunes without an exchange plan.
 
-// the handle serves norms and scaling, or the message saying why not (`device_form`: the call takes HBM pointers)
-static bool scale_serves(const spx_matrix_t *A, const char *what, bool device_form)
+// the handle serves norms and scaling, or the message saying why not (`device_form`: the call takes HBM pointers;
+// `want_symmetric`: the entry points of symmetric tunes ask)
+static bool scale_serves(const spx_matrix_t *A, const char *what, bool device_form, bool want_symmetric = false)
 {
     if (!A) { SETERROR_1(SPX_ERR_ARG_INVALID, "invalid matrix handle"); return false; }
-    if (A->symmetric) {
+    if (A->symmetric && !want_symmetric) {
         SETERROR_1(SPX_ERR_TUNED_MAT, (std::string(what) + ": the matrix was tuned as a symmetric one -- norms and "
-                   "scaling serve general tunes only").c_str());
+                   "scaling serve general tunes only (use spx_hip_mat_sym_norms / spx_hip_mat_sym_scale)").c_str());
+        return false;
+    }
+    if (!A->symmetric && want_symmetric) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, (std::string(what) + ": the matrix was tuned as a general one: spx_hip_mat_norms / "
+                   "spx_hip_mat_scale(A, d, d)").c_str());
         return false;
     }
     if (A->dist) {
@@ -2956,6 +2962,104 @@ try {
                         values_plan_digest(*A->values_plan, *A->host_stream, host_threads()) == A->pre_refresh_digest;
         } else {
             device_mat_scale_host(A->dev, dr, dc);
+        }
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    if (as_before) A->values_refreshed = false;
+    else values_were_refreshed(A);
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+// ---- the same for a matrix tuned as a symmetric one ----------------------------------------------------------
+// One vector: the norms of the rows are those of the columns, and only D * A * D keeps the matrix symmetric
+// (sym_scale_kernels.hip in HBM, host_mat_sym_* of mat_scale.cpp on the host copy of a host-only matrix).
+static bool sym_scale_serves(const spx_matrix_t *A, const char *what, bool device_form)
+{
+    return scale_serves(A, what, device_form, true);
+}
+
+spx_error_t spx_hip_mat_sym_norms(const spx_matrix_t *A_, int kind, spx_value_t *out_dev, void *stream)
+try {
+    spx_matrix_t *A = const_cast<spx_matrix_t *>(A_);
+    if (!sym_scale_serves(A, "spx_hip_mat_sym_norms", true)) return SPX_FAILURE;
+    if (kind < SPX_HIP_NORM_SUM_ABS || kind > SPX_HIP_NORM_MAX_ABS) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_sym_norms: kind is none of SPX_HIP_NORM_SUM_ABS, _SUM_SQ, _MAX_ABS");
+        return SPX_FAILURE;
+    }
+    if (!out_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_sym_norms: out is NULL"); return SPX_FAILURE; }
+    try {
+        device_mat_sym_norms(A->dev, kind, out_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_sym_norms_host(const spx_matrix_t *A_, int kind, spx_value_t *out)
+try {
+    spx_matrix_t *A = const_cast<spx_matrix_t *>(A_);
+    if (!sym_scale_serves(A, "spx_hip_mat_sym_norms_host", false)) return SPX_FAILURE;
+    if (kind < SPX_HIP_NORM_SUM_ABS || kind > SPX_HIP_NORM_MAX_ABS) {
+        SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_sym_norms_host: kind is none of SPX_HIP_NORM_SUM_ABS, _SUM_SQ, _MAX_ABS");
+        return SPX_FAILURE;
+    }
+    if (!out) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_sym_norms_host: out is NULL"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    try {
+        if (A->host_stream)
+            host_mat_sym_norms(*A->host_stream, kind, (size_t) A->nrows, (size_t) A->own_lo, (size_t) A->own_hi, out,
+                               host_threads());
+        else
+            device_mat_sym_norms_host(A->dev, kind, out);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_sym_scale(spx_matrix_t *A, const spx_value_t *d_dev, void *stream)
+try {
+    if (!sym_scale_serves(A, "spx_hip_mat_sym_scale", true)) return SPX_FAILURE;
+    if (!d_dev) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_sym_scale: d is NULL"); return SPX_FAILURE; }
+    try {
+        device_mat_sym_scale(A->dev, d_dev, stream);
+    } catch (const FatalError &e) {
+        SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());
+        return SPX_FAILURE;
+    }
+    // (the encoded partitions go stale as after spx_hip_mat_set_values)
+    if (!A->values_refreshed) {
+        std::lock_guard<std::mutex> lk(A->mtx);
+        values_were_refreshed(A);
+    }
+    return SPX_SUCCESS;
+} SPX_C_BOUNDARY(return SPX_FAILURE;)
+
+spx_error_t spx_hip_mat_sym_scale_host(spx_matrix_t *A, const spx_value_t *d)
+try {
+    if (!sym_scale_serves(A, "spx_hip_mat_sym_scale_host", false)) return SPX_FAILURE;
+    if (!d) { SETERROR_1(SPX_ERR_ARG_INVALID, "spx_hip_mat_sym_scale_host: d is NULL"); return SPX_FAILURE; }
+    std::lock_guard<std::mutex> lk(A->mtx);
+    bool as_before = false;
+    try {
+        if (A->host_stream) {
+            // (the digest rule of spx_hip_mat_scale_host)
+            const bool digests = A->values_plan != nullptr;
+            if (digests && !A->values_refreshed && !A->parts.empty()) {
+                A->pre_refresh_digest = values_plan_digest(*A->values_plan, *A->host_stream, host_threads());
+                A->has_pre_refresh_digest = true;
+                A->edited_while_stale = false;
+            }
+            host_mat_sym_scale(*A->host_stream, (size_t) A->nrows, (size_t) A->own_lo, (size_t) A->own_hi, d, host_threads());
+            if (!digests) A->edited_while_stale = true;
+            as_before = digests && A->has_pre_refresh_digest && !A->edited_while_stale &&
+                        values_plan_digest(*A->values_plan, *A->host_stream, host_threads()) == A->pre_refresh_digest;
+        } else {
+            device_mat_sym_scale_host(A->dev, d);
         }
     } catch (const FatalError &e) {
         SETERROR_1(SPX_ERR_TUNED_MAT, e.what.c_str());

@@ -214,6 +214,18 @@ void device_mat_norms(DeviceMatrix *m, int kind, double *d_rows, double *d_cols,
 void device_mat_scale(DeviceMatrix *m, const double *d_dr, const double *d_dc, void *stream);
 void device_mat_norms_host(DeviceMatrix *m, int kind, double *h_rows, double *h_cols);
 void device_mat_scale_host(DeviceMatrix *m, const double *h_dr, const double *h_dc);
+// The same for a SYMMETRIC stream (sym_scale_kernels.hip; the caller keeps general and attached matrices away): one
+// vector of nrows doubles.  device_mat_sym_norms writes ALL nrows elements of d_out -- the diagonal's term on the
+// own rows, zero elsewhere -- then joins in the thin mirror list and one csx_sym_norms_kernel launch per launch of
+// the forward product: a value stored once counts for its row and its column, a value stored twice for the row of
+// each copy.  device_mat_sym_scale rewrites a(r,c) <- fl(fl(d[max(r,c)] * a) * d[min(r,c)]) in the stream, its float
+// twin, the diagonal array and the mirror list; it reads d wherever the entries reach, [0, own_hi).  Calling rules
+// as above.  device_sym_scale_lds: the dynamic LDS of a norms launch, in bytes (0: not a symmetric stream).
+void device_mat_sym_norms(DeviceMatrix *m, int kind, double *d_out, void *stream);
+void device_mat_sym_scale(DeviceMatrix *m, const double *d_d, void *stream);
+void device_mat_sym_norms_host(DeviceMatrix *m, int kind, double *h_out);
+void device_mat_sym_scale_host(DeviceMatrix *m, const double *h_d);
+size_t device_sym_scale_lds(const DeviceMatrix *m);
 size_t device_n_values(const DeviceMatrix *m);     // doubles in the stream's value array
 
 struct DeviceMatrixInfo {

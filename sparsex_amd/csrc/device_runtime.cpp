@@ -81,6 +81,9 @@ struct DeviceMatrix {
     bool deterministic = false;   // spx.gpu.deterministic: wave tiles + fixed-order hand-overs, pinned
     uint32_t *slot_col = nullptr;
     size_t n_slot_col = 0;
+    // norms and scaling of a symmetric stream (sym_scale_kernels.hip): the most rows, slots and slots + rows of a
+    // row-block
+    uint32_t sym_rows = 0, sym_slots = 0, sym_core = 0;
     // rows of SPX_RB_PRIVATE row-blocks, merged and ascending: the init pass of the atomic
     // hand-over leaves them out (empty when there are too many pieces to be worth it)
     std::vector<std::pair<size_t, size_t>> private_rows;
@@ -348,6 +351,18 @@ DeviceMatrix *device_upload(const GpuStream &s, size_t nrows, size_t ncols,
         m->n_fix_idx = s.fix_idx.size();
         place.put(&m->slot_col, s.slot_group_col);
         m->n_slot_col = s.slot_group_col.size();
+    }
+    if (symmetric) {
+        // (norms and scaling of the stream where it lies: every family walks the plain passes and hands its slots
+        // over by slot_col, which therefore is on the device wherever a row-block has slots)
+        for (const SpxRowBlock &rb : s.rbs) {
+            m->sym_rows = std::max<uint32_t>(m->sym_rows, rb.n_rows);
+            m->sym_slots = std::max<uint32_t>(m->sym_slots, rb.n_slots);
+            m->sym_core = std::max<uint32_t>(m->sym_core, (uint32_t) rb.n_slots + rb.n_rows);
+        }
+        if (m->sym_slots && s.slot_group_col.empty())
+            throw FatalError("symmetric stream: row-blocks with transposed-sum slots and no slot columns");
+        if ((size_t) m->sym_core * sizeof(double) > 64u * 1024u) sym_norms_allow_lds(160u * 1024u);
     }
     if (!s.mirror_rows.empty()) {
         m->n_mirror_rows = (uint32_t) s.mirror_rows.size();
@@ -2086,6 +2101,118 @@ void device_mat_scale_host(DeviceMatrix *m, const double *h_dr, const double *h_
         throw;
     }
     (void) hipFree(d);
+}
+
+// ---- the same for a symmetric stream (sym_scale_kernels.hip) ----------------------------------------------------
+// One vector: the norms of the rows are those of the columns, and only D * A * D keeps the matrix symmetric.  The
+// row-block launches walk the plain pass table whatever family the product runs; the diagonal array and the thin
+// mirror list of a row slice have small kernels of their own.
+size_t device_sym_scale_lds(const DeviceMatrix *m);
+
+static void need_symmetric_stream(const DeviceMatrix *m, const char *what)
+{
+    if (!m->symmetric)
+        throw FatalError(std::string(what) + ": the matrix was tuned as a general one: spx_hip_mat_norms / spx_hip_mat_scale(A, d, d)");
+    if (!m->dvalues) throw FatalError(std::string(what) + ": the symmetric stream holds no diagonal array");
+    if (m->sym_slots && !m->slot_col)
+        throw FatalError(std::string(what) + ": the columns of the transposed-sum slots are not on the device");
+}
+
+void device_mat_sym_norms(DeviceMatrix *m, int kind, double *d_out, void *stream_)
+{
+    need_symmetric_stream(m, "sym_norms");
+    need_own_device(m);
+    if (kind != NORM_SUM_ABS && kind != NORM_SUM_SQ && kind != NORM_MAX_ABS) throw FatalError("sym_norms: no such kind");
+    if (!d_out || !m->nrows) return;
+    m->launched_since_edit = true;
+    launch_sym_norms_init(kind, stream_, d_out, m->nrows, m->dvalues, m->own_lo, m->own_hi, m->mirror_rows, m->mirror_ptr,
+                          m->mirror_val, m->n_mirror_rows);
+    SymNormArgs a{};
+    a.rbs = m->rbs; a.values = m->values; a.cidx = m->cidx; a.segrows = m->segrows;
+    a.passes = m->passes; a.descs = m->descs;
+    a.out = d_out; a.slot_col = m->slot_col; a.pass_stride = m->pass_stride;
+    const size_t lds = device_sym_scale_lds(m);
+    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
+        const uint32_t blocks = 8u * m->xcd_longest[ph];
+        if (blocks) launch_sym_norms(kind, m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+void device_mat_sym_scale(DeviceMatrix *m, const double *d_d, void *stream_)
+{
+    need_symmetric_stream(m, "sym_scale");
+    need_own_device(m);
+    if (!d_d) return;
+    m->launched_since_edit = true;
+    SymScaleArgs a{};
+    a.rbs = m->rbs; a.values = m->values; a.cidx = m->cidx; a.segrows = m->segrows;
+    a.passes = m->passes; a.descs = m->descs;
+    a.d = d_d; a.values_rw = m->values; a.values_f32 = m->values_f32; a.pass_stride = m->pass_stride;
+    const size_t lds = (((size_t) m->sym_rows + 1u) & ~(size_t) 1) * sizeof(double);
+    for (size_t ph = 0; ph < m->xcd_split.size(); ++ph) {
+        const uint32_t blocks = 8u * m->xcd_longest[ph];
+        if (blocks) launch_sym_scale(m->waves, blocks, lds, stream_, a, m->xcd_split[ph]);
+    }
+    launch_sym_scale_rest(stream_, m->dvalues, m->own_lo, m->own_hi - m->own_lo, m->mirror_rows, m->mirror_ptr,
+                          m->mirror_col, m->mirror_val, m->n_mirror_rows, d_d);
+    HIP_CHECK(hipGetLastError());
+}
+
+// (the host forms: a temporary buffer of nrows doubles, the matrix' own stream, a wait)
+void device_mat_sym_norms_host(DeviceMatrix *m, int kind, double *h_out)
+{
+    need_symmetric_stream(m, "sym_norms");
+    need_own_device(m);
+    if (!h_out || !m->nrows) return;
+    if (!m->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking));
+    hipStream_t st = m->host_stream;
+    double *d = nullptr;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), m->nrows * sizeof(double)));
+    try {
+        // (values a client's streams are still writing are not ordered against this stream: wait for them as
+        // device_poke does, once)
+        quiesce_before_edit(m);
+        device_mat_sym_norms(m, kind, d, st);
+        HIP_CHECK(hipMemcpyAsync(h_out, d, m->nrows * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        m->launched_since_edit = false;
+    } catch (...) {
+        (void) hipStreamSynchronize(st);
+        (void) hipFree(d);
+        throw;
+    }
+    (void) hipFree(d);
+}
+
+void device_mat_sym_scale_host(DeviceMatrix *m, const double *h_d)
+{
+    need_symmetric_stream(m, "sym_scale");
+    need_own_device(m);
+    if (!h_d || !m->nrows) return;
+    if (!m->host_stream) HIP_CHECK(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking));
+    hipStream_t st = m->host_stream;
+    double *d = nullptr;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), m->nrows * sizeof(double)));
+    try {
+        HIP_CHECK(hipMemcpyAsync(d, h_d, m->nrows * sizeof(double), hipMemcpyHostToDevice, st));
+        // (products a client enqueued on streams of its own are not ordered against this one: wait for them as
+        // device_poke does, once)
+        quiesce_before_edit(m);
+        device_mat_sym_scale(m, d, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        m->launched_since_edit = false;
+    } catch (...) {
+        (void) hipStreamSynchronize(st);
+        (void) hipFree(d);
+        throw;
+    }
+    (void) hipFree(d);
+}
+
+size_t device_sym_scale_lds(const DeviceMatrix *m)
+{
+    return m->symmetric ? (((size_t) m->sym_core + 1u) & ~(size_t) 1) * sizeof(double) : 0;
 }
 
 size_t device_n_values(const DeviceMatrix *m) { return m->n_values; }

@@ -18,4 +18,14 @@ void host_mat_norms(const GpuStream &s, int kind, size_t nrows, size_t ncols, si
 // formed); positions without an element keep their bits
 void host_mat_scale(GpuStream &s, size_t nrows, size_t ncols, const double *dr, const double *dc, unsigned nthreads);
 
+// The same on the host copy of a SYMMETRIC stream (csx_sym_norms_kernel, csx_sym_scale_kernel of
+// sym_scale_kernels.hip).  host_mat_sym_norms writes all n elements of out: a value held once (tiles, read-once
+// segments) counts for its row and its column, a value held twice for the row of each copy, the diagonal array for
+// the own rows [own_lo, own_hi), the thin mirror list for its rows.  host_mat_sym_scale: values[p] <-
+// fl(fl(d[max(r,c)] * values[p]) * d[min(r,c)]), the diagonal array and the mirror list alike.  A position with
+// row == column (the zero of a block that closes over the diagonal) is neither counted nor written, and a +-0 of a
+// tile pass keeps its bits.
+void host_mat_sym_norms(const GpuStream &s, int kind, size_t n, size_t own_lo, size_t own_hi, double *out, unsigned nthreads);
+void host_mat_sym_scale(GpuStream &s, size_t n, size_t own_lo, size_t own_hi, const double *d, unsigned nthreads);
+
 }  // namespace spx

@@ -1,9 +1,9 @@
 // spmv_launch.hpp -- what host code needs to launch the CSX interpreter: the kernel arguments, the
-// XCD-aware row-block order, the kernel families and the launchers of the ten interpreter translation
+// XCD-aware row-block order, the kernel families and the launchers of the eleven interpreter translation
 // units (spmv_kernels.hip, spmv_xw_kernels.hip, spmv_sx_kernels.hip, spmv_t_kernels.hip, spmv_mv_kernels.hip,
 // spmv_mv_f32_kernels.hip, spmv_mvr_kernels.hip, spmv_mvr_f32_kernels.hip, spmv_mvsym_kernels.hip,
-// scale_kernels.hip).  Plain C++: no HIP header, so that the host runtime (device_runtime.cpp) is compiled by the
-// host compiler.
+// scale_kernels.hip, sym_scale_kernels.hip).  Plain C++: no HIP header, so that the host runtime
+// (device_runtime.cpp) is compiled by the host compiler.
 #pragma once
 
 #include "gpu_format.h"
@@ -137,6 +137,36 @@ struct NormArgs : StreamArgs {
     uint32_t pass_stride;
 };
 void launch_norms(int kind, int waves, unsigned blocks, size_t lds_bytes, void *stream, const NormArgs &a, const XcdSplit &xs);
+
+// sym_scale_kernels.hip: the same for a SYMMETRIC stream -- tiles, read-once segments, lower copies and mirror
+// images; the plain pass headers and descriptors, one launch per entry of the matrix' XCD splits.
+// csx_sym_scale_kernel: a(r,c) <- fl(fl(d[max(r,c)] * a) * d[min(r,c)]) in place and in the float twin, where there
+// is one.  lds_bytes: the most rows of a row-block (d of its rows).  launch_sym_scale_rest: the diagonal array of
+// the own rows [own_lo, own_lo + n_own) and the thin mirror list (n_mirror rows), which have no twin.
+struct SymScaleArgs : StreamArgs {
+    const double *d;         // nrows doubles
+    double *values_rw;       // StreamArgs::values, to be written
+    float *values_f32;       // its float twin, or null
+    uint32_t pass_stride;
+};
+void launch_sym_scale(int waves, unsigned blocks, size_t lds_bytes, void *stream, const SymScaleArgs &a, const XcdSplit &xs);
+void launch_sym_scale_rest(void *stream, double *dvalues, size_t own_lo, size_t n_own, const uint32_t *mrows,
+                           const uint32_t *mptr, const uint32_t *mcol, double *mval, uint32_t n_mirror, const double *d);
+// csx_sym_norms_kernel<KIND>: out[i] (+)= the terms of row i of the full matrix.  A value stored once counts for
+// its row and, through the row-block's transposed-sum slots in LDS, for its column; a value stored twice for the
+// row of each copy.  Atomics on top of launch_sym_norms_init, which writes all n elements of `out`: the term of the
+// diagonal on the own rows, zero elsewhere, and then joins in the thin mirror list.  lds_bytes: the most slots +
+// rows of a row-block (sym_norms_allow_lds: beyond the default 64 KB).
+struct SymNormArgs : StreamArgs {
+    double *out;
+    const uint32_t *slot_col;  // the first column of every group of eight transposed-sum slots
+    uint32_t pass_stride;
+};
+void launch_sym_norms(int kind, int waves, unsigned blocks, size_t lds_bytes, void *stream, const SymNormArgs &a,
+                      const XcdSplit &xs);
+void launch_sym_norms_init(int kind, void *stream, double *out, size_t n, const double *dvalues, size_t own_lo,
+                           size_t own_hi, const uint32_t *mrows, const uint32_t *mptr, const double *mval, uint32_t n_mirror);
+void sym_norms_allow_lds(size_t bytes);
 
 // spmv_mv_kernels.hip: the multi-vector product, K = 2, 4 or 8 vectors per pass over the plain stream.
 // Column-major blocks: vector j of X at x + j * ldx, of Y at y + j * ldy.

@@ -16,8 +16,11 @@ namespace spx {
 // matrix need not hold (it stays the zero the tune put there); every other position visited is a real element
 // (pass padding and lanes beyond a piece's length are not visited).  Rows and columns are NOT checked against
 // the matrix: a caller that indexes by them does.
+// for_each_stored_value_of_pass: the same walk, which also reports the kind of the pass that holds the position
+// (SPX_PASS_*): on a symmetric stream SPX_PASS_SYMTILE and SPX_PASS_SYMSEG hold an entry ONCE, for its row and its
+// column; every other kind holds one copy of an entry stored twice (mat_scale.cpp).
 template <typename Visit>
-void for_each_stored_value(const GpuStream &s, unsigned nthreads, Visit visit)
+void for_each_stored_value_of_pass(const GpuStream &s, unsigned nthreads, Visit visit)
 {
     constexpr size_t RB_CHUNK = 16;
     const size_t n_rb = s.rbs.size();
@@ -35,22 +38,30 @@ void for_each_stored_value(const GpuStream &s, unsigned nthreads, Visit visit)
                         const int64_t row = (int64_t) rb.row0 + SPX_SEGROW_ROW(sr);
                         for (uint32_t w = 0; w < W && w < SPX_SEGROW_LEN(sr); ++w)
                             visit(vbase + spx_pass_value_index(l, w, nseg, W), row,
-                                  gather_col(s, rb, ps, (size_t) ps.elem0 + l + (size_t) w * nseg), false);
+                                  gather_col(s, rb, ps, (size_t) ps.elem0 + l + (size_t) w * nseg), false, ps.kind);
                     } else if (ps.kind == SPX_PASS_SYMTILE) {
                         // (a cell of a tile that the matrix does not hold stays the zero the tune put there)
                         int64_t r, c0;
                         tile_lane(s, rb, ps, l, r, c0);
                         for (uint32_t w = 0; w < 8; ++w)
-                            visit(vbase + spx_pass_value_index(l, w, nseg, 8), (int64_t) rb.row0 + r, c0 + w, true);
+                            visit(vbase + spx_pass_value_index(l, w, nseg, 8), (int64_t) rb.row0 + r, c0 + w, true, ps.kind);
                     } else {
                         int64_t r, c0;
                         unit_lane(s, rb, ps, l, r, c0);
                         for (uint32_t w = 0; w < W; ++w)
-                            visit(vbase + spx_pass_value_index(l, w, nseg, W), (int64_t) rb.row0 + r, c0 + w, false);
+                            visit(vbase + spx_pass_value_index(l, w, nseg, W), (int64_t) rb.row0 + r, c0 + w, false, ps.kind);
                     }
                 }
             }
         }
+    });
+}
+
+template <typename Visit>
+void for_each_stored_value(const GpuStream &s, unsigned nthreads, Visit visit)
+{
+    for_each_stored_value_of_pass(s, nthreads, [&](size_t pos, int64_t row, int64_t col, bool may_be_absent, uint8_t) {
+        visit(pos, row, col, may_be_absent);
     });
 }
 

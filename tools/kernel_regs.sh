@@ -2,8 +2,8 @@
 # Registers, scratch and LDS of every kernel of the interpreter's translation units (cross-compiled, no GPU
 # needed):
 #   tools/kernel_regs.sh [pattern] [extra hipcc flags]
-# SPX_TU: the units, default all ten ("spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_t_kernels spmv_mv_kernels
-# spmv_mv_f32_kernels spmv_mvr_kernels spmv_mvr_f32_kernels spmv_mvsym_kernels scale_kernels"; any other .hip file of
+# SPX_TU: the units, default all eleven ("spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_t_kernels spmv_mv_kernels
+# spmv_mv_f32_kernels spmv_mvr_kernels spmv_mvr_f32_kernels spmv_mvsym_kernels scale_kernels sym_scale_kernels"; any other .hip file of
 # sparsex_amd/csrc works too).  They compile side by side and leave their assembly in /tmp/spx_asm/<unit>.s
 # Names are printed demangled and whole (llvm-cxxfilt of the ROCm tree or c++filt; without either, mangled), less
 # the return type, the namespace and the parameter list: csx_spmv_mv_kernel<MvArgs, double, (MvFamily)2, 8, 4> is
@@ -12,7 +12,7 @@
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p /tmp/spx_asm
-units=${SPX_TU:-spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_t_kernels spmv_mv_kernels spmv_mv_f32_kernels spmv_mvr_kernels spmv_mvr_f32_kernels spmv_mvsym_kernels scale_kernels}
+units=${SPX_TU:-spmv_kernels spmv_xw_kernels spmv_sx_kernels spmv_t_kernels spmv_mv_kernels spmv_mv_f32_kernels spmv_mvr_kernels spmv_mvr_f32_kernels spmv_mvsym_kernels scale_kernels sym_scale_kernels}
 for tu in $units; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -munsafe-fp-atomics -Iinclude -Isparsex_amd/csrc \
         ${2:-} -S --cuda-device-only -o /tmp/spx_asm/$tu.s sparsex_amd/csrc/$tu.hip 2>/dev/null &

@@ -11,13 +11,25 @@ every one of 5 rounds -- tools/matmat_bench.py --f32's `alternate` -- and each r
     set-values        spx_hip_mat_set_values         (needs a values plan: --no-set-values leaves it out)
 
     python3 tools/scale_bench.py [--configs e240,cant,webbase] [--edge 240] [--values-f32]
+    python3 tools/scale_bench.py --sym [--configs e240,cant,nd24k]
+
+--sym: the same workloads tuned as symmetric ones AND as general ones, both handles in the process, the variants of the
+two alternating in the same rounds:
+
+    sym-forward       spx_hip_matvec_kernel on the symmetric tune (what the ratios are taken against)
+    sym-scale         spx_hip_mat_sym_scale(d)
+    sym-norms-<kind>  spx_hip_mat_sym_norms
+    forward, scale (dr = dc = d), norms-<kind>-both   the general tune of the same matrix, for comparison
+
+Its gates: the max-abs norms of the symmetric handle against numpy bit for bit, its sum-abs norms against |A| 1
+(relative 1e-9), and after one scaling the symmetric forward product against the CSR product of the scaled matrix.
 
 The scale vectors hold +1 and -1 (a hash of the index): every multiplication is done, and a matrix scaled any
 number of times keeps its magnitudes.  Gates, before anything is timed: the max-abs norms of the handle against
 numpy over the CSR arrays bit for bit (rows) and the sum-abs norms against |A| 1 and |A|^T 1 (relative 1e-9),
 and after one scaling the forward product against the CSR product of the
 scaled matrix (relative 1e-6).  One JSON line per config; the configs of one run share a process, so their times
-compare.  General tunes only (symmetric ones are not served)."""
+compare."""
 import argparse
 import json
 import os
@@ -149,6 +161,92 @@ def run(torch, cfg, edge, threads, values_f32, with_set_values):
     return out
 
 
+def run_sym(torch, cfg, edge, threads, values_f32):
+    """--sym: the symmetric and the general tune of one workload side by side"""
+    import scipy.sparse as sp
+    from sparsex_amd import synth
+    wl = CONFIGS[cfg][0]
+
+    def note(msg):
+        print("[scale_bench --sym] %s: %s" % (cfg, msg), file=sys.stderr, flush=True)
+    csr = workload(wl, edge)
+    rp, ci, va, n = csr
+    nnz = int(rp[-1])
+    note("%s, %d rows, %d nonzeros" % (wl, n, nnz))
+    base = {"spx.rt.nr_threads": threads, "spx.rt.device": torch.cuda.current_device(), "spx.rt.keep_encoded": "false"}
+    t0 = time.perf_counter()
+    S = bench.tune(csr, dict(base, **{"spx.matrix.symmetric": "true",
+                                      **({"spx.gpu.values_f32": "all"} if values_f32 else {})}))
+    G = bench.tune(csr, dict(base, **{"spx.matrix.symmetric": "false",
+                                      **({"spx.gpu.values_f32": "true"} if values_f32 else {})}))
+    tune_s = time.perf_counter() - t0
+    note("both tuned in %.1f s" % tune_s)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = torch.cuda.current_stream().cuda_stream
+    d_h = signs(n, 1)
+    d = torch.from_numpy(d_h).to(dev)
+    xh = synth.random_x(n, seed=42)
+    x = torch.from_numpy(xh).to(dev)
+    y, out, rows, cols = (torch.full((n,), float("nan"), dtype=torch.float64, device=dev) for _ in range(4))
+
+    absa = np.abs(va)
+    absm = sp.csr_matrix((absa, ci, rp), shape=(n, n))
+    S.hip_mat_sym_norms(0, out.data_ptr(), stream)
+    torch.cuda.synchronize()
+    want = absm @ np.ones(n)
+    ok_norms = bool((np.abs(out.cpu().numpy() - want) <= 1e-9 * want).all())
+    S.hip_mat_sym_norms(2, out.data_ptr(), stream)
+    torch.cuda.synchronize()
+    want = np.maximum.reduceat(np.append(absa, 0.0), rp[:-1].astype(np.int64))
+    want[np.diff(rp) == 0] = 0.0
+    ok_norms &= bool(np.array_equal(out.cpu().numpy(), want))
+    del absa, absm, want
+    S.hip_mat_sym_scale(d.data_ptr(), stream)
+    S.hip_matvec_kernel(bench.ALPHA, x.data_ptr(), 0.0, y.data_ptr(), stream)
+    torch.cuda.synchronize()
+    ref = bench.ALPHA * (d_h * (sp.csr_matrix((va, ci, rp), shape=(n, n)) @ (d_h * xh)))
+    yh = y.cpu().numpy()
+    ok_scale = bool(np.isfinite(yh).all()) and bool((np.abs(yh - ref) <= 1e-6 * np.abs(ref) + 1e-12 * np.abs(ref).max()).all())
+    del ref, yh
+    note("gates: norms %s, scaled product %s" % (ok_norms, ok_scale))
+    S.hip_mat_sym_scale(d.data_ptr(), stream)                     # (and back: the signs square to one)
+    torch.cuda.synchronize()
+
+    fns = {
+        "sym-forward": lambda: S.hip_matvec_kernel(bench.ALPHA, x.data_ptr(), 0.0, y.data_ptr(), stream),
+        "sym-scale": lambda: S.hip_mat_sym_scale(d.data_ptr(), stream),
+        "forward": lambda: G.hip_matvec_kernel(bench.ALPHA, x.data_ptr(), 0.0, y.data_ptr(), stream),
+        "scale": lambda: G.hip_mat_scale(d.data_ptr(), d.data_ptr(), stream),
+    }
+    for name, kind in KINDS:
+        fns["sym-norms-%s" % name] = lambda kind=kind: S.hip_mat_sym_norms(kind, out.data_ptr(), stream)
+        fns["norms-%s-both" % name] = lambda kind=kind: G.hip_mat_norms(kind, rows.data_ptr(), cols.data_ptr(), stream)
+    t_est = alternate(torch, {"sym-forward": fns["sym-forward"]}, 1, 1)["sym-forward"][0]
+    reps = int(min(max(0.02 / max(t_est, 1e-7), 2), 200)) & ~1
+    t = alternate(torch, fns, reps, bench.BATCHES)
+    fwd = t["sym-forward"][0]
+    si, gi = S.info(), G.info()
+    s_values, g_values = int(si.value_bytes) // 8, int(gi.value_bytes) // 8
+    res = {"config": cfg + "-sym", "workload": wl, "edge": edge if wl == "syn-nlpkkt" else None, "nrows": n, "nnz": nnz,
+           "sym_stream_values": s_values, "general_stream_values": g_values, "values_f32": bool(values_f32),
+           "waves": int(si.waves), "sym_tiles": int(si.sym_tiles), "sym_segments": int(si.sym_segments),
+           "sym_pipeline": int(si.sym_pipeline), "rowblocks": int(si.n_rowblocks),
+           "us": {k: round(1e6 * v[0], 2) for k, v in t.items()}, "spread": {k: round(v[1], 3) for k, v in t.items()},
+           "vs_sym_forward": {k: round(v[0] / fwd, 3) for k, v in t.items()},
+           "sym_scale_gb_per_s": round(16.0 * s_values / t["sym-scale"][0] / 1e9, 1),
+           "scale_gb_per_s": round(16.0 * g_values / t["scale"][0] / 1e9, 1),
+           "reps": reps, "gate_norms": ok_norms, "gate_scaled_product": ok_scale, "parity": ok_norms and ok_scale,
+           "tune_seconds": round(tune_s, 2),
+           "protocol": "warm-up calls, hipEvent time per batch of calls, the variants of both handles alternating inside "
+                       "every one of %d rounds, median and (max - min) / median; scale vectors of +-1; gb_per_s = 16 B "
+                       "per stream value over the time of the scaling" % bench.BATCHES}
+    S.destroy()
+    G.destroy()
+    del x, y, out, rows, cols, d
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--configs", default="e240,cant,webbase", help="the general configs of tools/matmat_bench.py")
@@ -156,13 +254,17 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--values-f32", action="store_true", help="tune with the float copy: scale rewrites it as well")
     ap.add_argument("--no-set-values", action="store_true", help="no values plan, no set-values variant")
+    ap.add_argument("--sym", action="store_true", help="the symmetric tune next to the general one (see above)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
     ok = True
     for cfg in args.configs.split(","):
-        line = json.dumps(run(torch, cfg, args.edge, args.threads, args.values_f32, not args.no_set_values))
+        if args.sym:
+            line = json.dumps(run_sym(torch, cfg, args.edge, args.threads, args.values_f32))
+        else:
+            line = json.dumps(run(torch, cfg, args.edge, args.threads, args.values_f32, not args.no_set_values))
         print(line, flush=True)
         ok &= json.loads(line)["parity"]
         if args.out:
